@@ -6,19 +6,21 @@ One "step" = one IPM iteration unit (sedumi.m:450-473) on
 Workload at N=1: BASELINE.json configs[1], examples/control07.mat itself -- the hot-path inputs of the reference's
 example (At after pretransfo, K, the scaling of the "rand" golden tag, rhs) travel as tests/golden/control07.npz
 (generated from /root/reference by tests/golden/make_golden.py).  `--workload control07_like` is the synthetic
-problem of the same shape; `nb`, `maxcut<n>`, `blockdiag` are the shapes of configs[2..4].  The default N=1 run also
-measures those other configs briefly in the same process and reports them under "other_configs".
+problem of the same shape; `nb`, `maxcut<n>`, `blockdiag` are the shapes of configs[2..4].  `--other-configs` (N=1)
+also measures those other configs briefly in the same process and reports them under "other_configs".
 
 N>1 (launched with torch.distributed.run, one rank per GPU): ONE unit per step, sharded the way the workload shards
 (SURVEY.md 8e): single-supernode workloads form ADA' as column panels per rank + one RCCL all-gather (factor and
 solves replicated -- they do not shard); the block-diagonal workload deals its independent subtrees to the ranks
 (all-gather of the solution only).  `--shard replicas` runs independent units per rank instead (weak scaling).
 
-Prints ONE compact JSON line (rank 0, < 4 KB, strict JSON: `compact_line`) with the fields the driver expects plus `roofline`
-and `cpu_baseline` (the unmodified reference MEX, naive BLAS-1, one host core) and a handful of scalar extras.  Everything
-else the run measures -- per-kernel times, the phases, `cpu_baseline_blas` (the reference linked to the host's OpenBLAS),
-`pcie_inclusive`, `mex_inclusive` (the unit through the built mexFunction shims: what an unmodified sedumi.m pays), the
-other configs with `--other-configs` -- goes to `profiles/bench_detail_<tag>.json`, whose path the line names.
+Prints ONE compact JSON line (rank 0, < 4 KB, strict JSON: `compact_line`) with the fields the driver expects.  A plain run
+sets up, warms up, times `--steps` units and prints the line; its `roofline` and `cpu_baseline` are null.  `--full` adds
+everything else: `roofline` and `cpu_baseline` (the unmodified reference MEX, naive BLAS-1, one host core) and a handful of
+scalar extras in the line, and -- per-kernel times, the phases, `pcie_inclusive`, `mex_inclusive` (the unit through the built
+mexFunction shims: what an unmodified sedumi.m pays), `whole_solve_weighted`, with `--other-configs` also `cpu_baseline_blas`
+(the reference linked to the host's OpenBLAS) and the other configs -- in `profiles/bench_detail_<tag>.json`, whose path the
+line names.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (`dump_outputs`).
 
 `python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment) re-executes itself under
 `python -m torch.distributed.run --nproc-per-node N` on 127.0.0.1 and passes rank 0's line through.
@@ -102,8 +104,39 @@ def write_detail(full, tag):
         return None
 
 
-def emit(full, tag, extras=None):
-    print(compact_line(full, extras, write_detail(full, tag)), flush=True)
+def emit(full, tag, extras=None, detail=True):
+    print(compact_line(full, extras, write_detail(full, tag) if detail else None), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every non-empty array as <path>/<name>.npy in float64, at most `limit` bytes in all.  When the arrays are
+    larger, the small ones are written whole and each larger one as a fixed sample of its entries (positions drawn with seed 0,
+    kept in order), so that two runs with the same arguments write the same positions."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for k, v in arrays.items()}
+    arrays = {k: v for k, v in arrays.items() if v.size}
+    budget = limit // 8
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        share = budget // (len(arrays) - i)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        budget -= a.size
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def plan_outputs(plan):
+    """What a caller of the unit receives from the resident plan: ADA' and absd (getada3), L.L on its pattern and L.d (blkchol),
+    blkchol's Lskip / Ladd as one status per row (0 kept, 1 skipped, 2 added) and the pivot value of those rows (0 elsewhere), the
+    solution y of the last solve.  Every array has a length fixed by the problem, whatever the pivots."""
+    (si, sv), (ai, av) = plan.pivots()
+    status, value = np.zeros(plan.m), np.zeros(plan.m)
+    status[si], value[si] = 1.0, sv
+    status[ai], value[ai] = 2.0, av
+    return {"ada": plan.download("ada"), "absd": plan.download("absd"), "L": plan.download("lpr"), "d": plan.download("d"),
+            "y": plan.download("y"), "pivot_status": status, "pivot_value": value}
 
 
 def relaunch(args):
@@ -243,18 +276,24 @@ def bench_lpdense(args, device):
         for _ in range(NSOLVE):
             plan.ldlsolve()
     el = time_steps(plan, step, args.steps, args.warmup)
-    ph = np.zeros(4)
-    nprof = min(args.steps, 20)
-    for _ in range(nprof):
-        plan.timer_begin(0); plan.getada(); plan.timer_end(0)
-        plan.timer_begin(1); plan.blkchol(PARS, True); plan.timer_end(1)
-        t0 = time.perf_counter(); plan.deninfac(smult, 500.0); plan.sync(); ph[2] += 1e3 * (time.perf_counter() - t0)
-        plan.timer_begin(3)
-        for _ in range(NSOLVE):
-            plan.ldlsolve()
-        plan.timer_end(3)
-        ph[[0, 1, 3]] += [plan.timer_ms(0), plan.timer_ms(1), plan.timer_ms(3)]
-    ph /= nprof
+    if args.dump_outputs:
+        lden, dden = plan.lden()
+        dump_outputs(args.dump_outputs, dict(plan_outputs(plan), dden=dden, **{"lden_" + k: v for k, v in lden.items()}))
+    phases = None
+    if args.full:
+        ph = np.zeros(4)
+        nprof = min(args.steps, 20)
+        for _ in range(nprof):
+            plan.timer_begin(0); plan.getada(); plan.timer_end(0)
+            plan.timer_begin(1); plan.blkchol(PARS, True); plan.timer_end(1)
+            t0 = time.perf_counter(); plan.deninfac(smult, 500.0); plan.sync(); ph[2] += 1e3 * (time.perf_counter() - t0)
+            plan.timer_begin(3)
+            for _ in range(NSOLVE):
+                plan.ldlsolve()
+            plan.timer_end(3)
+            ph[[0, 1, 3]] += [plan.timer_ms(0), plan.timer_ms(1), plan.timer_ms(3)]
+        ph /= nprof
+        phases = {"ada_ms": ph[0], "factor_ms": ph[1], "deninfac_ms_host_timed": ph[2], "solves_ms": ph[3], "dpr1fact_on_host_fallback": bool(host[0])}
     emit({
         "metric": "IPM iters/sec (ADA' form+factor+solve)", "value": args.steps / el, "unit": "IPM iters/s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -262,9 +301,7 @@ def bench_lpdense(args, device):
         "config": {"workload": f"{P.name}: sparse LP with dense columns (SURVEY.md 8(d) config 3 variant), m={P.m}, nnz(L)={plan.nnzL}, "
                                f"nsuper={np.asarray(L['xsuper']).size - 1}; unit = getada, blkchol, deninfac (sparse fwblkslv x 8 + dpr1fact), "
                                f"{NSOLVE}x(fwblkslv, fwdpr1, ./Ld, bwdpr1, bwblkslv)", "parallelism": "single GPU"},
-        "roofline": None, "cpu_baseline": None,
-        "phases_ms_per_step": {"ada_ms": ph[0], "factor_ms": ph[1], "deninfac_ms_host_timed": ph[2], "solves_ms": ph[3],
-                               "dpr1fact_on_host_fallback": bool(host[0])}}, "lpdense_n1")
+        "roofline": None, "cpu_baseline": None, "phases_ms_per_step": phases}, "lpdense_n1", detail=args.full)
     plan.close()
 
 
@@ -747,10 +784,12 @@ def bench_subtrees(args, rank, local_rank, world, torch, dist, coll_dev):
     solver.upload_scaling(d, ud, P)
     solver.upload_rhs(rhs)                             # inputs resident in HBM before the timed region
 
+    last = [None]
+
     def step():
         solver.factor()
         for _ in range(NSOLVE):
-            solver.solve_resident()
+            last[0] = solver.solve_resident()
 
     def sync():
         if solver.plan is not None:
@@ -773,6 +812,16 @@ def bench_subtrees(args, rank, local_rank, world, torch, dist, coll_dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        y = np.zeros(P.m)                              # the gathered solution in the problem's order (SubtreeShardedSolver.solve)
+        if last[0] is None:
+            y[solver.cols] = solver.plan.download("y", solver.cols.size)
+        else:
+            host, seg = last[0].cpu().numpy(), solver.send.numel()
+            for q, c in enumerate(solver.cols_of):
+                if c is not None and c.size:
+                    y[c] = host[q * seg:q * seg + c.size]
+        dump_outputs(args.dump_outputs, {"y": y})
     if rank == 0:
         emit({
             "metric": "IPM iters/sec (ADA' form+factor+solve)", "value": args.steps / elapsed, "unit": "IPM iters/s", "n_gpus": world,
@@ -781,7 +830,7 @@ def bench_subtrees(args, rank, local_rank, world, torch, dist, coll_dev):
             "config": {"workload": f"{P.name}: block-diagonal SDP (BASELINE.json configs[4]), m={P.m}, {nblk} independent subtrees; "
                                    f"unit = getada1+2+3, blkchol, {NSOLVE}x(fwblkslv,./d,bwblkslv)",
                        "parallelism": f"{world} rank(s): subtrees per rank {[int(c.size // mper) for c in solver.cols_of]}, all-gather of y only"},
-            "roofline": None, "cpu_baseline": None}, f"blockdiag_n{world}")
+            "roofline": None, "cpu_baseline": None}, f"blockdiag_n{world}", detail=args.full)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -800,11 +849,12 @@ def bench_separator(args, rank, local_rank, world, torch, dist, coll_dev):
     rhs = np.random.default_rng(0).standard_normal(n * n)
     dev = coll_dev if dist is not None else torch.device("cuda", local_rank)
     solver = sd.SeparatorShardedSolver(X, device_index=local_rank, device=dev)
+    last = [None]
 
     def step():
         solver.factor(X.data, PARS)
         for _ in range(NSOLVE):
-            solver.solve(rhs)
+            last[0] = solver.solve(rhs)
 
     def sync():
         solver.plan.sync()
@@ -825,6 +875,8 @@ def bench_separator(args, rank, local_rank, world, torch, dist, coll_dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": last[0].cpu().numpy()})
     if rank == 0:
         own = [int(np.sum((solver.owner == r) & ~solver.top)) for r in range(world)]
         emit({
@@ -835,7 +887,7 @@ def bench_separator(args, rank, local_rank, world, torch, dist, coll_dev):
                                    "right-hand side uploaded per solve",
                        "parallelism": f"{world} rank(s): {int(solver.top.sum())} separator supernodes on rank 0, subtree supernodes per rank {own}; "
                                       "reduce of the subtree roots' fronts, reduce of their update vectors, broadcast of the separators' solution"},
-            "roofline": None, "cpu_baseline": None}, f"grid_n{world}")
+            "roofline": None, "cpu_baseline": None}, f"grid_n{world}", detail=args.full)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -855,15 +907,22 @@ def main():
                          "factor/solves replicated in both (one dense supernode does not shard); replicas = independent units per "
                          "rank (weak scaling, no collective); blockcyclic = columns for ADA' + ONE dense front factored block-column-cyclically "
                          "(sedumi_amd.dist.BlockCyclicFactor: a broadcast per 64-column panel), solves replicated")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel roofline and phases, the PCIe- and MEX-inclusive tiers, "
+                         "the iteration-weighted whole-solve figure, the CPU baseline of the reference; writes the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB in all: a fixed "
+                         "sample of the entries of the larger arrays beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--other-configs", action="store_true",
-                    help="also measure the other BASELINE configs (both scalings of the reference examples, maxcut4000, blockdiag, the maxcut8000 solve "
-                         "leg), the OpenBLAS-linked CPU baseline and the lazy MEX tiers: minutes, all of it into the detail file only")
+                    help="(implies --full) also measure the other BASELINE configs (both scalings of the reference examples, maxcut4000, blockdiag, the "
+                         "maxcut8000 solve leg), the OpenBLAS-linked CPU baseline and the lazy MEX tiers: minutes, all of it into the detail file only")
     ap.add_argument("--no-other-configs", action="store_true", help="(accepted for older command lines; other configs are off unless --other-configs)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (one launch per step)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / process-group / line plumbing only, on CPU; nothing is measured")
     ap.add_argument("--tag", default=None, help="suffix of profiles/bench_detail_<workload>_n<N>[_<tag>].json")
     args = ap.parse_args()
+    args.full = args.full or args.other_configs
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(relaunch(args))
@@ -961,8 +1020,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan_outputs(plan))
 
-    if bc is not None:                                   # (the per-kernel profile re-runs the unit on this plan alone: not with a front spread over ranks)
+    if not args.full:
+        roof, phases = None, None
+    elif bc is not None:                                 # (the per-kernel profile re-runs the unit on this plan alone: not with a front spread over ranks)
         roof, phases = None, {"factor": {"frac_of_fp64_matrix_peak": None}, "solve": {"frac_of_hbm_peak": None}}
     else:
         roof, phases = profile_unit(plan, P, ud, min(max(args.steps, 20), 50))
@@ -971,7 +1034,7 @@ def main():
         base = base_blas = pcie = mexleg = weighted = None
         others = []
         headline = args.workload == "control07" and world == 1
-        if world == 1:
+        if world == 1 and args.full:
             pcie = pcie_inclusive(plan, P, d, ud, rhs, min(args.steps, 20))
             plan.upload("rhs", rhs); plan.ldlsolve()
             mexleg = mex_inclusive(P, L, ADA, Q, d, ud, rhs, qpr, min(args.steps, 30), plan.download("y"))
@@ -1037,8 +1100,8 @@ def main():
                   "mex_inclusive_value": mexleg.get("value") if isinstance(mexleg, dict) else None,
                   "whole_solve_weighted_value": weighted and weighted["value"],
                   "factor_frac_of_fp64_matrix_peak": phases["factor"]["frac_of_fp64_matrix_peak"],
-                  "solves_frac_of_hbm_peak": phases["solve"]["frac_of_hbm_peak"]}
-        emit(out, f"{args.workload}_n{world}" + (f"_{args.tag}" if args.tag else ""), extras)
+                  "solves_frac_of_hbm_peak": phases["solve"]["frac_of_hbm_peak"]} if args.full else None
+        emit(out, f"{args.workload}_n{world}" + (f"_{args.tag}" if args.tag else ""), extras, detail=args.full)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -53,6 +53,29 @@ def test_detail_file_is_strict_json(tmp_path, monkeypatch):
     assert len(d["other_configs"]) == 50 and d["other_configs"][0]["v"] is None
 
 
+def test_dump_outputs_float64_within_the_limit_and_the_same_sample_every_time(tmp_path):
+    rng = np.random.default_rng(1)
+    arrays = {"small": np.arange(10, dtype=np.int64), "big": rng.standard_normal(5000), "bigger": rng.standard_normal((100, 90)), "empty": np.zeros(0)}
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, limit=8 * 3000)
+    assert not (tmp_path / "a" / "empty.npy").exists()                                   # nothing empty is written
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays if k != "empty"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 8 * 3000
+    assert np.array_equal(got["small"], np.arange(10))                                      # whole when it fits its share
+    assert 0 < got["big"].size < 5000 and np.all(np.isin(got["big"], arrays["big"]))       # a sample of the entries, in order
+    assert np.array_equal(got["big"], arrays["big"][np.isin(arrays["big"], got["big"])])
+    for k in got:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / (k + ".npy")))
+    bench.dump_outputs(str(tmp_path / "c"), arrays)                                       # (the default limit: everything whole)
+    assert np.array_equal(np.load(tmp_path / "c" / "bigger.npy"), arrays["bigger"].ravel())
+
+
+def test_full_and_dump_outputs_are_options_of_the_command_line():
+    text = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120).stdout
+    assert "--full" in text and "--dump-outputs" in text
+
+
 def _run(argv, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra or {})

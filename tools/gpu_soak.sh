@@ -8,7 +8,7 @@ timeout 100 python tests/tools/soak_def.py 30 > $OUT/soak_def.txt 2>&1
 tail -2 $OUT/soak_def.txt
 timeout 300 python -m pytest tests/test_gpu_parity.py -m gpu -q -k "one_launch_front or maxcut or sweeps or many_small or golden or iteration" > $OUT/factor_tests.txt 2>&1
 tail -2 $OUT/factor_tests.txt
-timeout 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 300 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 timeout 400 bash tools/profile_round.sh ${TAG}_control07 control07 100 > $OUT/prof_control07.log 2>&1
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
 timeout 200 bash tools/profile_round.sh ${TAG}_maxcut4000 maxcut4000 20 nopmc > $OUT/prof_maxcut4000.log 2>&1
