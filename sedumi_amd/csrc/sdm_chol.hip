@@ -1788,6 +1788,13 @@ __device__ SDM_NOINLINE void front_rows_diag(SDM_GP(double) Fs_, SDM_GP(const do
     }
     if (blk < 2) continue;
     __syncthreads();                                                  // Lt of the columns up to 16 blk + 15 is complete
+    if (blk == 3) {
+      // S and the wave tiles are dead (the substitution is over), Lt is not: S / Lc of the LDL' (Lc overlays the wave tiles, not
+      // Lt) are prepared beside the update's last k-steps instead of behind them
+      static_assert(NB * NB <= 4 * (NB * 17), "Lc of the LDL' must end before Lt");
+      double *Lc = RB;
+      for (int j = ty; j < NB; j += NW) { S[tx][j] = (tx == j && tx >= kbn) ? 1.0 : 0.0; Lc[j * NB + tx] = 0.0; }
+    }
     // k-steps of the update whose columns are final: 0 .. 11 after block 2, 12 .. 15 after block 3
     for (int kk = (blk == 2 ? 0 : 48); kk < (blk == 2 ? 48 : 64); kk += 4) {
       const int k = kk + lk;
@@ -1796,10 +1803,7 @@ __device__ SDM_NOINLINE void front_rows_diag(SDM_GP(double) Fs_, SDM_GP(const do
       for (int a = 0; a < 2; a++) acc[a] = SDM_MFMA_F64_16x16x4(bv, Lt[(2 * wi + a) * (NB * 17) + k * 17 + li], acc[a]);
     }
   }
-  __syncthreads();                                                    // S, the wave tiles and Lt are dead: S / Lc of the LDL' overlay them
-  double *Lc = RB;
-  for (int j = ty; j < NB; j += NW) { S[tx][j] = (tx == j && tx >= kbn) ? 1.0 : 0.0; Lc[j * NB + tx] = 0.0; }
-  __syncthreads();
+  __syncthreads();                                                    // S / Lc of the LDL' are cleared
 #pragma unroll
   for (int a = 0; a < 2; a++)
 #pragma unroll
