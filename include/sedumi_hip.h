@@ -281,7 +281,9 @@ int sdm_plan_pivots(sdm_plan *p, sdm_int *nskip, sdm_int *skip_idx, double *skip
                     sdm_int *nadd, sdm_int *add_idx, double *add_val);
 /* Solves on the resident factor: "y" <- op("rhs").
  *  fw:  y = L \ rhs(perm)         bw:  y(perm) = L' \ rhs
- *  ldl: y(perm) = L' \ ( (L \ rhs(perm)) ./ d )   (wrapPcg.m:56-59, no dense cols) */
+ *  ldl: y(perm) = L' \ ( (L \ rhs(perm)) ./ d )   (wrapPcg.m:56-59, no dense cols)
+ * If a workgroup of a merged sweep launch gave up waiting for another one, the plan's next read-back reports it as an error:
+ * that solve's output is unusable, the factor stays resident and the plan's later solves take the separate launches. */
 int sdm_plan_fwsolve(sdm_plan *p);
 int sdm_plan_bwsolve(sdm_plan *p);
 int sdm_plan_ldlsolve(sdm_plan *p);
@@ -289,7 +291,8 @@ int sdm_plan_ldlsolve(sdm_plan *p);
 /* hipGraph capture of a sequence of asynchronous plan calls (getada, blkchol, fw/bw/ldlsolve -- no uploads, downloads,
  * pivots or timers inside): begin, issue the calls once (they are recorded, not executed), end -> graph id;
  * sdm_plan_graph_launch replays the whole sequence with one launch on the plan's stream.  The captured sequence keeps
- * the parameters (pivot tolerances, buffers) it was recorded with. */
+ * the parameters (pivot tolerances, buffers) it was recorded with, and the launches: after a time-out the plan's later
+ * calls leave the one-launch factor or the merged sweeps, a graph recorded before keeps them (capture it again). */
 int sdm_plan_graph_begin(sdm_plan *p);
 int sdm_plan_graph_end(sdm_plan *p, int *graph_id);
 int sdm_plan_graph_launch(sdm_plan *p, int graph_id);
@@ -394,7 +397,7 @@ int sdm_plan_solve_stats(sdm_plan *p, sdm_int *nblocks, sdm_int *nbad, double *m
  *   front_layout: etree level, arena slice ("fronts": foff, fsize), update-vector slice ("wvec": woff, ms), columns (first, ns);
  *   blkchol_begin: permuteP + pivot thresholds ("ub"[2] = max diagonal, to be max-reduced across the ranks);
  *   blkchol_levels(l0, l1, extend_only): extend-add into the fronts of levels l0 .. l1-1 and (unless extend_only) their LDL';
- *   blkchol_end: the inverses for the solves;
+ *   blkchol_end: the inverses for the solves (_levels and _end are errors without a blkchol_begin before them);
  *   solve_levels(what, l0, l1) on the right-hand side in "rhs": what = 1 assembly of the fronts' right-hand sides (own entries +
  *     children's update vectors, in "wvec"), 2 the forward sweep of the levels without that assembly, 3 both, 4 the backward
  *     sweep of levels l1-1 .. l0 (reads the ancestors' solution from "xfin", writes "y").
@@ -409,19 +412,20 @@ int sdm_plan_solve_levels(sdm_plan *p, int what, sdm_int l0, sdm_int l1);
 /* ---- One front across GPUs (SURVEY.md 8e row blkchol, "block-cyclic dense LDL' with panel broadcasts"; sedumi_amd.dist.BlockCyclicFactor).
  * The ranks hold the same plan of ONE dense front (nsuper = 1, e.g. MAXCUT) on the launch-per-panel path (sdm_plan_set_one_launch_fronts(p, 0)
  * before set_chol) and the same ADA' values.  Tile column c (64 columns) of the front belongs to rank (c / blk) % world:
- *   set_column_owner(world, rank, blk)   before blkchol_begin; world = 1 gives the plan everything back;
- *   blkchol_panels(l0, l1, pan0, pan1)   the panel launches pan0 .. pan1-1 of the levels: the owner of tile column q factors panel q
+ *   blkchol_begin                        as above;
+ *   blkchol_panels(l0, l1, pan0, pan1, world, rank, blk)
+ *                                        the panel launches pan0 .. pan1-1 of the levels: the owner of tile column q factors panel q
  *                                        (cholonBlk, blkchol2.c:96-167, + the rows below it), every rank applies the trailing updates that
  *                                        are due (precorrect, blkchol2.c:346-420) to ITS tile columns -- per tile the operations and their
- *                                        order are those of the single plan: the same bits;
+ *                                        order are those of the single plan: the same bits.  The ownership holds for these launches
+ *                                        only; world = 1 (rank 0, any blk) owns everything, as every other factorisation of the plan does;
  *   panel_record(panel, unpack, &off, &n) after launch `panel`: its owner packs d, lb, the pivot decisions, the front's progress counters and the
  *                                        transposed diagonal block into the plan buffer "panelrec" (unpack = 0); the others store a received
  *                                        record (unpack = 1); unpack < 0 only answers.  off / n = the slice of "fronts" that holds the panel's columns.  The caller
  *                                        broadcasts both from the owner (what blkLDL's relinking, blkchol2.c:550-554, turns into when the
  *                                        supernode is spread over ranks) before anybody launches panel + 1;
  *   blkchol_end                           as above (every rank then holds the whole factor; the inverses for the solves are built by each). */
-int sdm_plan_set_column_owner(sdm_plan *p, int world, int rank, int blk);
-int sdm_plan_blkchol_panels(sdm_plan *p, sdm_int l0, sdm_int l1, sdm_int pan0, sdm_int pan1);
+int sdm_plan_blkchol_panels(sdm_plan *p, sdm_int l0, sdm_int l1, sdm_int pan0, sdm_int pan1, int world, int rank, int blk);
 int sdm_plan_panel_record(sdm_plan *p, sdm_int panel, int unpack, sdm_int *front_offset, sdm_int *front_nelem);
 
 /* ---- process-wide resident state behind the mexFunction shims (csrc/sdm_mexcache.hip).  Every .mex

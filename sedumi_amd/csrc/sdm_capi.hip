@@ -11,10 +11,26 @@ void set_error(const std::string &msg) { g_err = msg; }
 }  // namespace sdm
 using namespace sdm;
 
-// every read-back of a plan passes through here after its stream synchronise: a spin inside one of THIS plan's panel
-// launches (or merged sweep launches, sdm_solve.hip: merged_wait) that gave up makes the results unusable (the plan is marked not factored by chol_wait_timeouts)
+// every read-back of a plan passes through here after its stream synchronise: a spin inside one of THIS plan's launches that gave up
+// makes the results unusable -- of a factor launch: the plan is marked not factored; of a merged sweep launch (sdm_solve.hip: merged_wait):
+// that solve's, the factor stays and the plan's next solves run unmerged (chol_wait_timeouts)
+static const char *const FACTOR_TIMEOUT = "blkchol: a workgroup timed out waiting for another one inside a factor launch";
 static void check_plan_health(sdm_plan *p) {
-  if (chol_wait_timeouts(p)) throw std::runtime_error("blkchol: a workgroup timed out waiting for another one inside a launch (factor panel or merged sweep)");
+  const int t = chol_wait_timeouts(p);
+  if (t & TMO_FACTOR) throw std::runtime_error(FACTOR_TIMEOUT);
+  if (t & TMO_SWEEP) throw std::runtime_error("solve: a workgroup timed out waiting for another one inside a merged sweep launch (the factor stays; the next solves run unmerged)");
+}
+// the pivot parameters of a factorisation: blkchol.c:292-294 defaults, abstol >= 0 (blkchol.c:303)
+static sdm_cholpars chol_pars(const sdm_cholpars *pars) {
+  sdm_cholpars q = {1e-12, 5e2, 1e-20};
+  if (pars) q = *pars;
+  if (q.abstol < 0.0) q.abstol = 0.0;
+  return q;
+}
+// the steps of a staged factorisation between sdm_plan_blkchol_begin and _end
+static void require_begun(sdm_plan *p, const char *fn) {
+  if (!p->has_chol) throw std::runtime_error(std::string(fn) + ": no symbolic factor set");
+  if (!p->chol.begun) throw std::runtime_error(std::string(fn) + ": no factorisation begun (sdm_plan_blkchol_begin)");
 }
 
 #define SDM_TRY try {
@@ -213,9 +229,7 @@ int sdm_plan_copy(sdm_plan *p, const char *name, void *devptr, sdm_int offset, s
 int sdm_plan_blkchol(sdm_plan *p, const sdm_cholpars *pars, int use_absd) {
   SDM_TRY
   if (!p->has_chol) throw std::runtime_error("sdm_plan_blkchol: no symbolic factor set");
-  sdm_cholpars q = {1e-12, 5e2, 1e-20};           // blkchol.c:292-294 defaults
-  if (pars) q = *pars;
-  if (q.abstol < 0.0) q.abstol = 0.0;              // blkchol.c:303
+  const sdm_cholpars q = chol_pars(pars);
   p->dense.factored = false;                        // the dense-column factors belong to the previous L, d
   chol_factor(p, q.canceltol, q.maxu, q.abstol, use_absd);
   SDM_CATCH
@@ -225,8 +239,9 @@ int sdm_plan_blkchol_wait(sdm_plan *p, const sdm_cholpars *pars, int use_absd) {
   for (int attempt = 0; ; attempt++) {
     if (sdm_plan_blkchol(p, pars, use_absd)) throw std::runtime_error(g_err);
     SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-    if (!chol_wait_timeouts(p)) break;                               // (a time-out switches the plan to the launch-per-panel path)
-    if (attempt == 1) throw std::runtime_error("blkchol: a workgroup timed out waiting for another one inside a launch (factor panel or merged sweep)");
+    // (a factor time-out switches the plan to the launch-per-panel path; one of a merged sweep before it only switches merging off)
+    if (!(chol_wait_timeouts(p) & TMO_FACTOR)) break;
+    if (attempt == 1) throw std::runtime_error(FACTOR_TIMEOUT);
   }
   SDM_CATCH
 }
@@ -256,35 +271,30 @@ int sdm_plan_front_layout(sdm_plan *p, sdm_int *nlevels, sdm_int *level, sdm_int
 int sdm_plan_blkchol_begin(sdm_plan *p, const sdm_cholpars *pars, int use_absd) {
   SDM_TRY
   if (!p->has_chol) throw std::runtime_error("sdm_plan_blkchol_begin: no symbolic factor set");
-  sdm_cholpars q = {1e-12, 5e2, 1e-20};
-  if (pars) q = *pars;
-  if (q.abstol < 0.0) q.abstol = 0.0;
+  const sdm_cholpars q = chol_pars(pars);
   p->dense.factored = false;
   chol_begin(p, q.canceltol, q.maxu, q.abstol, use_absd);
   SDM_CATCH
 }
 // ---- one dense front factored block-column-cyclically by several ranks (include/sedumi_hip.h: "One front across GPUs")
-int sdm_plan_set_column_owner(sdm_plan *p, int world, int rank, int blk) {
+int sdm_plan_blkchol_panels(sdm_plan *p, sdm_int l0, sdm_int l1, sdm_int pan0, sdm_int pan1, int world, int rank, int blk) {
   SDM_TRY
-  if (world < 1 || world > 255 || rank < 0 || rank >= world || blk < 1 || blk > 255) throw std::runtime_error("sdm_plan_set_column_owner: need 1 <= world <= 255, 0 <= rank < world, 1 <= blk <= 255");
-  p->chol.own = world == 1 ? 0 : (world | rank << 8 | blk << 16);
-  SDM_CATCH
-}
-int sdm_plan_blkchol_panels(sdm_plan *p, sdm_int l0, sdm_int l1, sdm_int pan0, sdm_int pan1) {
-  SDM_TRY
-  if (!p->has_chol) throw std::runtime_error("sdm_plan_blkchol_panels: no symbolic factor set");
+  require_begun(p, "sdm_plan_blkchol_panels");
+  if (world < 1 || world > 255 || rank < 0 || rank >= world || blk < 1 || blk > 255) throw std::runtime_error("sdm_plan_blkchol_panels: need 1 <= world <= 255, 0 <= rank < world, 1 <= blk <= 255");
+  if (world > 1 && p->chol.nsuper != 1) throw std::runtime_error("sdm_plan_blkchol_panels: block-cyclic ranks (world > 1) factor ONE dense front");
   for (int l = (int)std::max<sdm_int>(l0, 0); l < (int)std::min<sdm_int>(l1, p->chol.nlevels); l++)
     if (p->chol.lev_persist[l] && !p->chol.front_disabled)
       throw std::runtime_error("sdm_plan_blkchol_panels: the level is planned as ONE launch; call sdm_plan_set_one_launch_fronts(plan, 0) before sdm_plan_set_chol");
-  chol_levels(p, (int)l0, (int)l1, false, (int)pan0, (int)std::min<sdm_int>(pan1, 1 << 30));
+  const int own = world == 1 ? 0 : (world | rank << 8 | blk << 16);   // (k_ldl_panel: owns_col)
+  chol_levels(p, (int)l0, (int)l1, false, own, (int)pan0, (int)std::min<sdm_int>(pan1, 1 << 30));
   SDM_CATCH
 }
 int sdm_plan_panel_record(sdm_plan *p, sdm_int panel, int unpack, sdm_int *front_offset, sdm_int *front_nelem) {
   SDM_TRY
   if (!p->has_chol) throw std::runtime_error("sdm_plan_panel_record: no symbolic factor set");
-  if (unpack >= 0) chol_panel_record(p, (int)panel, unpack);            // (unpack < 0: only the slice of "fronts" is asked for)
   const CholPlan &C = p->chol;
   if (C.nsuper != 1 || panel < 0 || panel * NB >= C.sn_ns[0]) throw std::runtime_error("sdm_plan_panel_record: one dense front, 0 <= panel < its panels");
+  if (unpack >= 0) chol_panel_record(p, (int)panel, unpack);            // (unpack < 0: only the slice of "fronts" is asked for)
   const sdm_int k0 = panel * NB, kb = std::min<sdm_int>(NB, C.sn_ns[0] - k0);
   if (front_offset) *front_offset = C.sn_foff[0] + k0 * (sdm_int)C.sn_ld[0];
   if (front_nelem) *front_nelem = kb * (sdm_int)C.sn_ld[0];
@@ -292,11 +302,13 @@ int sdm_plan_panel_record(sdm_plan *p, sdm_int panel, int unpack, sdm_int *front
 }
 int sdm_plan_blkchol_levels(sdm_plan *p, sdm_int l0, sdm_int l1, int extend_only) {
   SDM_TRY
-  chol_levels(p, (int)l0, (int)l1, extend_only != 0);
+  require_begun(p, "sdm_plan_blkchol_levels");
+  chol_levels(p, (int)l0, (int)l1, extend_only != 0, /*own=*/0);
   SDM_CATCH
 }
 int sdm_plan_blkchol_end(sdm_plan *p) {
   SDM_TRY
+  require_begun(p, "sdm_plan_blkchol_end");
   chol_end(p);
   SDM_CATCH
 }

@@ -133,6 +133,7 @@ __host__ __device__ inline bool owns_col(int own, int c) {
 void chol_build(sdm_plan *P, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const sdm_int *perm,
                 sdm_int nsuper, const sdm_int *xsuper, const sdm_int *ADAjc, const sdm_int *ADAir) {
   CholPlan &C = P->chol;
+  C.begun = false;                                                   // (a staged factorisation of the previous factor ends here)
   C.m = m; C.nsuper = nsuper; C.nnzL = Ljc[m]; C.nnzADA = ADAjc[m];
   if (C.nnzADA >= (sdm_int)1 << 31) throw std::runtime_error("nnz(ADA) >= 2^31 not supported");
   C.Ljc.assign(Ljc, Ljc + m + 1);
@@ -2078,11 +2079,12 @@ void chol_begin(sdm_plan *P, const double canceltol, const double maxu, const do
     }
   }
   SDM_HIP_CHECK(hipGetLastError());
+  C.begun = true;
 }
 // levels l0 .. l1-1: children's update matrices into the fronts of the level (extend-add), then -- unless extend_only -- its LDL'
-void chol_levels(sdm_plan *P, int l0, int l1, bool extend_only, int pan0, int pan1) {
+void chol_levels(sdm_plan *P, int l0, int l1, bool extend_only, int own, int pan0, int pan1) {
   // pan0 .. pan1-1: of every level's panel launches only these (sdm_plan_blkchol_panels: ranks that factor one front block-cyclically
-  // exchange the finished panel between two launches); the extend-add of a level runs with its first launch
+  // exchange the finished panel between two launches, own says which tile columns are theirs); the extend-add of a level runs with its first launch
   CholPlan &C = P->chol;
   hipStream_t st = P->stream; (void)st;                              // (used by the emulator's launches of the follower only)
   FrontTab tab = front_tab(C);
@@ -2135,14 +2137,14 @@ void chol_levels(sdm_plan *P, int l0, int l1, bool extend_only, int pan0, int pa
 #ifdef SDM_EMU
       if (emu_concurrent() && (1 + L.ride_wgs) * L.nactive <= 200)   // as on the device: one launch, the roles wait for each other (one process per workgroup)
         SDM_KLAUNCH_CONCURRENT(P, k_ldl_panel, dim3(1 + L.ride_wgs, L.nactive), dim3(LDL_THREADS), PANEL_LDS_RIDE, C.fronts.p, C.frontsT.p, tab, list,
-                               L.panel, C.d.p, C.panel_ctx.p, C.upd_cnt.p, C.diag_cnt.p, 1, 0, C.tmo.dev(), C.own);
+                               L.panel, C.d.p, C.panel_ctx.p, C.upd_cnt.p, C.diag_cnt.p, 1, 0, C.tmo.dev(), own);
       else
       for (int phase = 1; phase <= 2; phase++)
 #else
       const int phase = 0;
 #endif
         SDM_KLAUNCH(P, k_ldl_panel, dim3(1 + L.ride_wgs, L.nactive), dim3(LDL_THREADS), PANEL_LDS_RIDE, C.fronts.p, C.frontsT.p, tab, list,
-                    L.panel, C.d.p, C.panel_ctx.p, C.upd_cnt.p, C.diag_cnt.p, 1, phase, C.tmo.dev(), C.own);
+                    L.panel, C.d.p, C.panel_ctx.p, C.upd_cnt.p, C.diag_cnt.p, 1, phase, C.tmo.dev(), own);
       if (L.lasttiles > 0)                                           // supernodes that end with this panel and have rows beyond
         SDM_KLAUNCH(P, k_ldl_update, dim3(L.lasttiles, L.nactive), dim3(256), 0, C.fronts.p, tab, list, L.panel, C.d.p, 1);
     }
@@ -2173,36 +2175,43 @@ void chol_panel_record(sdm_plan *P, int panel, int unpack) {
   if (C.nsuper != 1) throw std::runtime_error("panel records: block-cyclic factorisation is for ONE dense front");
   if (C.panelrec.n < (size_t)(4 * NB + 2 + NB * NB)) C.panelrec.alloc((size_t)(4 * NB + 2 + NB * NB));
   const int ns = C.sn_ns[0], k0 = panel * NB, kb = std::min(NB, ns - k0);
-  if (k0 >= ns) throw std::runtime_error("panel record: no such panel");
+  if (panel < 0 || k0 >= ns) throw std::runtime_error("panel record: no such panel");
   SDM_KLAUNCH(P, k_panel_record, dim3(8), dim3(256), 0, C.panelrec.p, C.d.p, C.lb.p, C.pivval.p, C.pivstat.p, C.upd_cnt.p, C.diag_cnt.p, C.frontsT.p, C.sn_first[0], k0, kb, 0,
               C.sn_toff[0], unpack);
 }
 void chol_end(sdm_plan *P) {
   if (!P->chol.follow) solve_prepare(P, /*sb_g_is_zero=*/true);      // inverses of the diagonal super-blocks for the solves (else: built behind the levels)
   SDM_HIP_CHECK(hipGetLastError());
+  P->chol.begun = false;
   P->factored = true;
 }
 void chol_factor(sdm_plan *P, const double canceltol, const double maxu, const double abstol, int use_absd) {
   chol_begin(P, canceltol, maxu, abstol, use_absd);
-  chol_levels(P, 0, P->chol.nlevels, false, 0, 1 << 30);
+  chol_levels(P, 0, P->chol.nlevels, false, /*own=*/0);
   chol_end(P);
 }
 
-// Non-zero when a workgroup gave up waiting for another one inside a launch (never expected; the results of that
-// factorisation are then unusable: the plan is marked "not factored", so the solves refuse to run on it).  Reads and
-// clears the plan's own flag (pinned host memory the kernels of THIS plan write to); call after a stream synchronise.
+// Non-zero when a workgroup gave up waiting for another one inside a launch (never expected).  Reads and clears the plan's own
+// flags (pinned host memory the kernels of THIS plan write to); call after a stream synchronise.
+//   TMO_FACTOR: the results of that factorisation are unusable: the plan is marked "not factored", so the solves refuse to run on it.
+//   TMO_SWEEP: the output of that solve is unusable, the factor is not touched: the plan's later sweeps run unmerged.
 int chol_wait_timeouts(sdm_plan *P) {
   CholPlan &C = P->chol;
   if (!C.tmo.host) return 0;
-  const int n = *(volatile int *)C.tmo.host;
-  if (n) {
-    *(volatile int *)C.tmo.host = 0; P->factored = false;
+  volatile int *flag = C.tmo.host;
+  const int r = (flag[0] ? TMO_FACTOR : 0) | (flag[1] ? TMO_SWEEP : 0);
+  if (r & TMO_FACTOR) {
+    flag[0] = 0; P->factored = false;
     // k_ldl_front needs ALL its workgroups resident and they wait for each other: another process on the same device (or a partition
     // smaller than the one the plan was built on) can keep some of them out until the bounded waits give up.  The launch-per-panel
     // path only ever waits for workgroups dispatched earlier, so this plan's later factorisations take that one.
     C.front_disabled = true; C.follow = false;
   }
-  return n;
+  if (r & TMO_SWEEP) {
+    // the same for the merged launches (sdm_solve.hip: merged_wait): the separate ones only wait for launches that came before them
+    flag[1] = 0; C.merge_disabled = true;
+  }
+  return r;
 }
 
 void chol_extract(sdm_plan *P, double *d_Lpr_out) {

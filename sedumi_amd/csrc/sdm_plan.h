@@ -103,7 +103,7 @@ struct HostFlag {
   ~HostFlag() { if (host) (void)hipHostFree(host); }
   void ensure() {
     if (host) return;
-    SDM_HIP_CHECK(hipHostMalloc((void **)&host, 4 * sizeof(int), 0));      // (CholPlan::noted uses two of them)
+    SDM_HIP_CHECK(hipHostMalloc((void **)&host, 4 * sizeof(int), 0));      // (CholPlan::noted and CholPlan::tmo use two of them)
     for (int i = 0; i < 4; i++) host[i] = 0;
   }
   int *dev() {
@@ -165,6 +165,7 @@ struct CholPlan {
   std::vector<char> sn_active;           // empty: every supernode; else the supernodes THIS plan factors and solves (the level lists hold only
                                          // these: the others keep their place in the arenas and are never touched by a launch -- sedumi_amd.dist)
   double pars_canceltol = 0, pars_maxu = 0, pars_abstol = 0; int pars_use_absd = 0;   // of the factorisation in progress (chol_begin .. chol_end)
+  bool begun = false;                    // that factorisation has begun and not ended (the staged entry points need one: sdm_capi.hip)
   std::vector<LevelLaunch> launches;     // factor panel launches in execution order
   std::vector<int> lev_first_launch;     // index into launches per level (+ sentinel)
   // device copies
@@ -182,11 +183,12 @@ struct CholPlan {
   std::vector<int> lev_maxT;       // its grid: tile rows of the tallest front ...
   std::vector<int> lev_ntw;        // ... plus this many tile workgroups per front
   DevBuf<int> upd_cnt;     // per front: finished tile workgroups of the updates that rode along with k_ldl_panel
-  int own = 0;             // block-cyclic ranks (sdm_plan_set_column_owner): world | rank << 8 | blk << 16, 0 = this plan owns every tile column (sdm_chol.hip: owns_col)
-  DevBuf<double> panelrec; // the record of one finished panel between those ranks (chol_panel_record)
+  DevBuf<double> panelrec; // the record of one finished panel between block-cyclic ranks (sdm_plan_blkchol_panels, chol_panel_record)
   DevBuf<PanelCtx> panel_ctx;   // what only workgroup 0 of k_ldl_panel needs, behind ONE kernel argument (uploaded when it changes)
   PanelCtx panel_ctx_host = {};
-  HostFlag tmo;            // raised by a spin inside a panel launch of THIS plan that gave up (chol_wait_timeouts)
+  HostFlag tmo;            // raised by a spin of THIS plan that gave up (chol_wait_timeouts): host[0] inside a launch of the factor (panel launches,
+                           // k_ldl_front, the inverse behind it or solve_prepare's), host[1] inside a merged sweep launch (sweep_tmo)
+  int *sweep_tmo() { return tmo.dev() + 1; }
   // ---- solves (sdm_solve.hip): per front and super-block of sbw columns one nb x nb array in the arena S = the explicit
   // inverse of that diagonal block of L (block P of front s at sn_soff[s] + P * sbw * sn_sld[s], leading dimension sn_sld[s])
   int sbw = SBW_MIN;                 // super-block width of this plan (solve_build: covers the widest front, at most SBW_MAX)
@@ -210,7 +212,8 @@ struct CholPlan {
   DevBuf<int> l_i128, l_items;       // work lists of the inversion: 128-column leaves (4 ints each), combine tiles (8 ints each, sorted by stage)
   int n_i128 = 0, n_items = 0;
   bool follow = false;               // every front is factored by k_ldl_front and inverted behind it by k_sinv_follow (no solve_prepare launches)
-  bool front_disabled = false;       // a launch of this plan timed out: its later factorisations take the launch-per-panel path (chol_wait_timeouts)
+  bool front_disabled = false;       // a factor launch of this plan timed out: its later factorisations take the launch-per-panel path (chol_wait_timeouts)
+  bool merge_disabled = false;       // a merged sweep launch of this plan timed out: its later sweeps run unmerged (chol_wait_timeouts)
   std::vector<int> lev_followT;      // grid.x of k_sinv_follow per level: tiles of the inverse of its widest front
   std::vector<int> stage_ptr;        // combine tiles of stage st (= 2 * level + (0: T, 1: X)) are l_items[stage_ptr[st] .. stage_ptr[st+1])
   std::vector<SolveLevel> slev;
@@ -435,11 +438,14 @@ void chol_build(sdm_plan *P, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, 
 void chol_factor(sdm_plan *P, const double canceltol, const double maxu, const double abstol, int use_absd);
 // the same in three steps (sdm_plan_blkchol_begin / _levels / _end: the multi-GPU layer reduces update matrices between levels)
 void chol_begin(sdm_plan *P, const double canceltol, const double maxu, const double abstol, int use_absd);
-void chol_levels(sdm_plan *P, int l0, int l1, bool extend_only, int pan0 = 0, int pan1 = 1 << 30);
+// own: the tile columns this plan factors (k_ldl_panel: owns_col) -- 0 all of them, else world | rank << 8 | blk << 16 (sdm_plan_blkchol_panels)
+void chol_levels(sdm_plan *P, int l0, int l1, bool extend_only, int own, int pan0 = 0, int pan1 = 1 << 30);
 void chol_panel_record(sdm_plan *P, int panel, int unpack);
 void chol_end(sdm_plan *P);
 void chol_forget_plan(sdm_plan *P);    // the plan is being destroyed (turn-taking of k_ldl_front launches)
-int chol_wait_timeouts(sdm_plan *P);   // non-zero: a spin inside a panel launch of this plan gave up since the last call (call after a stream sync)
+// a spin of this plan gave up since the last call (call after a stream sync): TMO_FACTOR inside a factor launch, TMO_SWEEP inside a merged sweep launch
+constexpr int TMO_FACTOR = 1, TMO_SWEEP = 2;
+int chol_wait_timeouts(sdm_plan *P);
 void chol_extract(sdm_plan *P, double *d_Lpr_out);           // device pointer, nnzL doubles
 void chol_load_factor(sdm_plan *P, const double *h_Lpr, const double *h_d = nullptr);   // host L values (and d) -> fronts (stand-alone solves)
 void vec_gather(sdm_plan *P, double *dst, const double *src, bool forward);  // dst[k]=src[perm[k]] / dst[perm[k]]=src[k]

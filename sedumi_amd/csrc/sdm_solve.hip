@@ -647,6 +647,8 @@ __device__ __forceinline__ double row_seg(const double *__restrict__ M, const do
   return a;
 }
 constexpr int SEGN = 1024;                                           // entries of a row one wavefront takes in one trip (8 loads of 16 bytes per lane)
+static_assert(SBW_MAX <= 2 * SEGN && SBW_MAX / 64 <= MC_N,
+              "merged sweeps: a row of a super-block takes at most two wavefront segments (tri_task), its chunks of 64 rows one counter each (merged_count)");
 // workgroup b, wavefront `wave` of a triangular block of nb rows -> t = the row's rank by length (its row has t + 1 entries; -1: none), seg of nseg
 __device__ __forceinline__ void tri_task(int nb, int b, int wave, int &t, int &seg, int &nseg) {
   const int n1 = min(nb, SEGN), wg1 = (n1 + 3) >> 2;
@@ -1315,10 +1317,19 @@ void solve_stats(sdm_plan *P, sdm_int *nblocks, sdm_int *nbad, double *max_growt
 constexpr int REFINE_STEPS = 2;
 // merged sweep launches (k_sfw_rows_diag): 0 never, 1 where rows beyond the next super-block exist, 2 every row launch of a one-front level
 static int sweep_merge_pre() { const char *e = getenv("SEDUMI_HIP_SWEEP_PRE"); return e ? std::max(0, atoi(e)) : PRE_WGS; }
-static int sweep_merge_level() {
+static int sweep_merge_level(const CholPlan &C) {
+  if (C.merge_disabled) return 0;                                  // (a merged launch of this plan timed out: chol_wait_timeouts)
   const char *e = getenv("SEDUMI_HIP_SWEEP_MERGE");               // (read per sweep: the tests switch it)
   return e ? atoi(e) : 1;
 }
+#ifdef SDM_EMU
+// (tests, emulator build only) the next n merged sweep launches report a time-out, as if one of their workgroups had given up waiting: a
+// counter of its own, apart from the factor's (emu_inject_timeouts), so that neither kind of launch takes the other's.  Returns the
+// injections still pending before the call.
+static int g_sweep_timeouts = 0;
+extern "C" int sdm_emu_inject_sweep_timeouts(int n) { const int left = g_sweep_timeouts; g_sweep_timeouts = n; return left; }
+static void emu_sweep_timeout(CholPlan &C) { if (g_sweep_timeouts > 0) { g_sweep_timeouts--; ((volatile int *)C.tmo.host)[1] = 1; } }
+#endif
 static bool solve_refines(CholPlan &C) {
   if (C.refine_mode != 1) return C.refine_mode == 2;
   if (C.noted.host) {
@@ -1355,7 +1366,7 @@ void solve_fw_batch(sdm_plan *P, const double *rhs, int64_t rhs_stride, double *
     if (!gather && (what & 1)) SDM_KLAUNCH(P, k_sfw_init, dim3(L.nfronts, 1, nrhs), dim3(ST), 0, tab, list, wv, rhs, C.d_perm.p, y, bt);
     if (!(what & 2)) continue;
     bool diag_done = false;                                          // (this super-block's diagonal role ran inside the row launch before it)
-    const int merge = sweep_merge_level();
+    const int merge = sweep_merge_level(C);
     const bool may_merge = merge && W > 256 && nrhs == 1 && !refine && tab.one && L.nsb >= 2;
     for (int Pb = 0; Pb < L.nsb; Pb++) {
       const int nbmax = std::min(W, L.maxns - Pb * W);
@@ -1377,11 +1388,14 @@ void solve_fw_batch(sdm_plan *P, const double *rhs, int64_t rhs_stride, double *
 #ifdef SDM_EMU
         // (tests/test_emu_concurrent.py: one process per workgroup, the diagonal role really waits for the urgent rows)
         if (emu_concurrent() && nrw + ndiag <= 256) SDM_KLAUNCH_CONCURRENT(P, k_sfw_rows_diag, dim3(nrw + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.LT.p, C.fronts.p, C.ST.p, tab, list, wv, rhs, C.d_perm.p, y, C.sb_g.p, thr, Pb,
-                    assign0, bt, zdiv, dscale, W, C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nrw - nurg, sweep_merge_pre()), ndiag, C.tmo.dev());
+                    assign0, bt, zdiv, dscale, W, C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nrw - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
         else
 #endif
         SDM_KLAUNCH(P, k_sfw_rows_diag, dim3(nrw + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.LT.p, C.fronts.p, C.ST.p, tab, list, wv, rhs, C.d_perm.p, y, C.sb_g.p, thr, Pb,
-                    assign0, bt, zdiv, dscale, W, C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nrw - nurg, sweep_merge_pre()), ndiag, C.tmo.dev());
+                    assign0, bt, zdiv, dscale, W, C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nrw - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
+#ifdef SDM_EMU
+        emu_sweep_timeout(C);
+#endif
         diag_done = true;
       } else if (L.maxns > (Pb + 1) * W)                             // the fronts' own rows of later super-blocks
         SDM_KLAUNCH(P, k_sfw_rows, dim3(W > SEGN ? (L.maxns - (Pb + 1) * W + 1) / 2 : (L.maxns - (Pb + 1) * W + 3) / 4, L.nfronts, nrhs), dim3(ST), 0, C.LT.p, tab, list, wv, rhs, C.d_perm.p, y, Pb,
@@ -1413,7 +1427,7 @@ static void solve_bw_inplace(sdm_plan *P, double *y, double *yout, const double 
     if (!(skip_plain_init && !L.below))
       SDM_KLAUNCH(P, k_sbw_init, dim3((L.maxns + SROWS - 1) / SROWS, L.nfronts), dim3(ST), 0, C.fronts.p, tab, list, y, C.xfin.p, dscale);
     bool diag_done = false;
-    const int merge = sweep_merge_level();
+    const int merge = sweep_merge_level(C);
     const bool may_merge = merge && W > 256 && !refine && tab.one && L.nsb >= 2;
     for (int Q = L.nsb - 1; Q >= 0; Q--) {
       const int nbmax = std::min(W, L.maxns - Q * W);
@@ -1433,11 +1447,14 @@ static void solve_bw_inplace(sdm_plan *P, double *y, double *yout, const double 
         const int nurg = W > SEGN ? W / 2 : W / 4, ndiag = tri_grid(W);
 #ifdef SDM_EMU
         if (emu_concurrent() && nst + ndiag <= 256) SDM_KLAUNCH_CONCURRENT(P, k_sbw_step_diag, dim3(nst + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout, C.d_perm.p, C.sb_g.p, thr, Q, W,
-                    C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nst - nurg, sweep_merge_pre()), ndiag, C.tmo.dev());
+                    C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nst - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
         else
 #endif
         SDM_KLAUNCH(P, k_sbw_step_diag, dim3(nst + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout, C.d_perm.p, C.sb_g.p, thr, Q, W,
-                    C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nst - nurg, sweep_merge_pre()), ndiag, C.tmo.dev());
+                    C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nst - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
+#ifdef SDM_EMU
+        emu_sweep_timeout(C);
+#endif
         diag_done = true;
       } else if (Q > 0) SDM_KLAUNCH(P, k_sbw_step, dim3(nst, L.nfronts), dim3(ST), 0, C.fronts.p, tab, list, y, C.xfin.p, Q, W);
     }

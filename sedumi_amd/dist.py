@@ -475,7 +475,8 @@ class SeparatorShardedSolver:
 class BlockCyclicFactor:
     """LDL' of ONE dense front (a single-supernode factor: MAXCUT, control07, every dense ADA') over the ranks, 1-D block-column-cyclic
     (SURVEY.md 8e row blkchol: "block-cyclic dense LDL' with panel broadcasts").  Every rank holds the same plan on the
-    launch-per-panel path and the same ADA' values; tile column c (64 columns) belongs to rank (c // blk) % world:
+    launch-per-panel path and the same ADA' values; tile column c (64 columns) belongs to rank (c // blk) % world -- for the panel
+    launches of this class only (Plan.blkchol_panels): any other factorisation of the plan still does all the work itself:
 
       for every panel q:   all ranks launch panel q -- its owner factors it (cholonBlk, blkchol2.c:96-167, and the rows below), every
                            rank applies the trailing updates that are due to ITS tile columns (precorrect, blkchol2.c:346-420);
@@ -507,7 +508,6 @@ class BlockCyclicFactor:
             plan.set_one_launch_fronts(False)                        # the launch-per-panel path: the panels are exchanged between its launches
             plan.set_chol(L, ADApat)
         self.plan = plan
-        self.plan.set_column_owner(self.world, self.rank, self.blk)
         self.npanel = (self.m + 63) // 64
         self.nrec = 4 * 64 + 2 + 64 * 64
         _, n0 = self.plan.panel_slice(0)
@@ -530,7 +530,7 @@ class BlockCyclicFactor:
         pl = self.plan
         pl.blkchol_begin(pars, use_absd)
         for q in range(self.npanel):
-            pl.blkchol_panels(0, 1, q, q + 1)
+            pl.blkchol_panels(0, 1, q, q + 1, self.world, self.rank, self.blk)
             if self.world == 1:
                 continue
             src = self.owner(q)

@@ -19,6 +19,16 @@ from . import capi
 from .capi import SdmError, check, f64, i64, pf, pi
 
 
+def _cholpars(pars):
+    """The pivot parameters of a factorisation from a pars dict (checkpars.m:144-168 defaults, abstol >= 0)."""
+    cp = capi.CholPars(1e-12, 5e5, 1e-20)
+    if pars:
+        cp.canceltol = float(pars.get("canceltol", cp.canceltol))
+        cp.maxu = float(pars.get("maxu", cp.maxu))
+        cp.abstol = max(float(pars.get("abstol", cp.abstol)), 0.0)
+    return cp
+
+
 class Plan:
     def __init__(self, device=0, stream=None):
         self._lib = capi.lib()
@@ -241,20 +251,12 @@ class Plan:
                                       C.c_int64(int(nelem)), 1 if to_plan else 0))
 
     def blkchol(self, pars=None, use_absd=True):
-        cp = capi.CholPars(1e-12, 5e5, 1e-20)          # checkpars.m:144-168
-        if pars:
-            cp.canceltol = float(pars.get("canceltol", cp.canceltol))
-            cp.maxu = float(pars.get("maxu", cp.maxu))
-            cp.abstol = max(float(pars.get("abstol", cp.abstol)), 0.0)
+        cp = _cholpars(pars)
         check(self._lib.sdm_plan_blkchol(C.c_void_p(self._p), C.byref(cp), 1 if use_absd else 0))
 
     def blkchol_wait(self, pars=None, use_absd=False):
         """blkchol, waited for, with the one recovery of sdm_plan_blkchol_wait (what blkchol.mex calls)."""
-        cp = capi.CholPars(1e-12, 5e5, 1e-20)
-        if pars:
-            cp.canceltol = float(pars.get("canceltol", cp.canceltol))
-            cp.maxu = float(pars.get("maxu", cp.maxu))
-            cp.abstol = max(float(pars.get("abstol", cp.abstol)), 0.0)
+        cp = _cholpars(pars)
         check(self._lib.sdm_plan_blkchol_wait(C.c_void_p(self._p), C.byref(cp), 1 if use_absd else 0))
 
     # ---- the factorisation and the solve level by level (sedumi_amd.dist.SeparatorShardedSolver)
@@ -273,24 +275,18 @@ class Plan:
         return out
 
     def blkchol_begin(self, pars=None, use_absd=True):
-        cp = capi.CholPars(1e-12, 5e5, 1e-20)
-        if pars:
-            cp.canceltol = float(pars.get("canceltol", cp.canceltol))
-            cp.maxu = float(pars.get("maxu", cp.maxu))
-            cp.abstol = max(float(pars.get("abstol", cp.abstol)), 0.0)
+        cp = _cholpars(pars)
         check(self._lib.sdm_plan_blkchol_begin(C.c_void_p(self._p), C.byref(cp), 1 if use_absd else 0))
 
     def blkchol_levels(self, l0, l1, extend_only=False):
         check(self._lib.sdm_plan_blkchol_levels(C.c_void_p(self._p), C.c_int64(int(l0)), C.c_int64(int(l1)), 1 if extend_only else 0))
 
     # ---- one dense front block-column-cyclically over several ranks (sedumi_amd.dist.BlockCyclicFactor)
-    def set_column_owner(self, world, rank, blk=1):
-        """Tile column c (64 columns) of the front belongs to rank (c // blk) % world; before blkchol_begin."""
-        check(self._lib.sdm_plan_set_column_owner(C.c_void_p(self._p), C.c_int(int(world)), C.c_int(int(rank)), C.c_int(int(blk))))
-
-    def blkchol_panels(self, l0, l1, pan0, pan1):
-        """The panel launches pan0 .. pan1-1 of the levels l0 .. l1-1 (launch-per-panel path)."""
-        check(self._lib.sdm_plan_blkchol_panels(C.c_void_p(self._p), C.c_int64(int(l0)), C.c_int64(int(l1)), C.c_int64(int(pan0)), C.c_int64(int(pan1))))
+    def blkchol_panels(self, l0, l1, pan0, pan1, world=1, rank=0, blk=1):
+        """The panel launches pan0 .. pan1-1 of the levels l0 .. l1-1 (launch-per-panel path), after blkchol_begin.  world > 1: tile
+        column c (64 columns) of the front belongs to rank (c // blk) % world, and these launches do the work of `rank` only."""
+        check(self._lib.sdm_plan_blkchol_panels(C.c_void_p(self._p), C.c_int64(int(l0)), C.c_int64(int(l1)), C.c_int64(int(pan0)), C.c_int64(int(pan1)),
+                                                C.c_int(int(world)), C.c_int(int(rank)), C.c_int(int(blk))))
 
     def panel_slice(self, panel):
         """(offset, nelem) of the slice of "fronts" that holds the columns of panel `panel` of the (one) front."""

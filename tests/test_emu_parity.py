@@ -527,6 +527,170 @@ def test_set_chol_after_a_timeout_keeps_the_plan_on_the_panel_path(refmex):
         P.close()
 
 
+def test_a_sweep_timeout_keeps_the_factor_and_only_stops_merging():
+    """A workgroup of a merged sweep launch (k_sfw_rows_diag / k_sbw_step_diag) that gave up waiting raises the plan's SWEEP flag, not
+    the factor's: that solve's read-back is an error, the factor stays -- the next solve on it returns the right y from the separate
+    launches, and the next factorisation still takes k_ldl_front.  The time-out is injected (emulator build: sdm_emu_inject_sweep_timeouts)."""
+    from hipemu import build_emu
+    from sedumi_amd import problem
+    from sedumi_amd.capi import SdmError
+    from sedumi_amd.plan import Plan
+    lib = ctypes.CDLL(build_emu.build())
+    m = 1100                                                    # super-blocks of 512: one merged launch per sweep (check_solve_widths)
+    rng = np.random.default_rng(m)
+    Lv = np.tril(rng.standard_normal((m, m)) * (0.5 / np.sqrt(m)), -1) + np.eye(m)
+    X = Lv @ np.diag(0.5 + rng.random(m)) @ Lv.T
+    b = rng.standard_normal(m)
+    want = np.linalg.solve(X, b)
+    merged = ("k_sfw_rows_diag", "k_sbw_step_diag")
+    P = Plan(0)
+    try:
+        P.set_solve_width(512)
+        P.set_chol(problem.dense_symbolic(m), problem.dense_pattern(m))
+        P.upload("ada", X.ravel(order="F"))
+        P.kprof(True)
+        P.blkchol(None, False)
+        P.upload("rhs", b)
+        lib.sdm_emu_inject_sweep_timeouts(1)
+        P.ldlsolve()
+        with pytest.raises(SdmError, match="merged sweep"):
+            P.download("y")
+        assert lib.sdm_emu_inject_sweep_timeouts(0) == 0        # it was taken by the first merged launch
+        prof = P.kprof_summary()
+        assert "k_ldl_front" in prof and all(k in prof for k in merged), sorted(prof)
+        P.kprof(False)
+        P.kprof(True)
+        P.ldlsolve()                                            # no new factorisation
+        assert relerr(P.download("y"), want) < TOL
+        prof = P.kprof_summary()
+        assert not any(k in prof for k in merged), sorted(prof)
+        P.kprof(False)
+        P.kprof(True)
+        P.blkchol_wait(None, False)
+        assert "k_ldl_front" in P.kprof_summary()              # (no factor time-out: the plan keeps the one-launch path)
+        P.kprof(False)
+        P.ldlsolve()
+        assert relerr(P.download("y"), want) < TOL
+    finally:
+        lib.sdm_emu_inject_sweep_timeouts(0)
+        P.close()
+
+
+def _dense_front(m, seed):
+    """(L, ADA pattern, ADA values) of ONE dense front of order m with nine dependent columns: the pivot lists are not empty."""
+    from sedumi_amd import problem
+    rng = np.random.default_rng(seed)
+    B = rng.standard_normal((m, m - 9))
+    return problem.dense_symbolic(m), problem.dense_pattern(m), (B @ B.T / m).ravel(order="F")
+
+
+def _panel_plan(L, pat, vals):
+    """a plan of that front on the launch-per-panel path, its ADA' values uploaded"""
+    from sedumi_amd.plan import Plan
+    p = Plan(0)
+    p.set_one_launch_fronts(False)
+    p.set_chol(L, pat)
+    p.upload("ada", vals)
+    return p
+
+
+def test_block_cyclic_ownership_holds_for_its_own_panel_launches_only():
+    """sdm_plan_blkchol_panels takes the block-cyclic ownership of the tile columns as arguments: after launches that did the share of
+    rank 1 of 2, a plain blkchol of the same plan factors the whole front -- L, d and the pivot lists bit for bit those of a fresh plan.
+    (Kept as plan state, the ownership once made every later panel launch skip the other rank's columns: a silently wrong factor.)
+    Block-cyclic ranks on a factor of several supernodes are refused."""
+    import scipy.linalg
+    from sedumi_amd import mex, problem
+    from sedumi_amd.capi import SdmError
+    from sedumi_amd.plan import Plan
+    pars = {"canceltol": 1e-12, "maxu": 5e5, "abstol": 1e-20}
+    front, npanel = _dense_front(200, 1), (200 + 63) // 64
+    one, p = _panel_plan(*front), _panel_plan(*front)
+    try:
+        one.blkchol(pars, False)
+        p.blkchol_begin(pars, False)
+        for q in range(npanel):
+            p.blkchol_panels(0, 1, q, q + 1, world=2, rank=1, blk=1)
+        p.blkchol_end()
+        p.blkchol(pars, False)
+        assert np.array_equal(p.download("lpr"), one.download("lpr")) and np.array_equal(p.download("d"), one.download("d"))
+        (s1, _), (a1, _) = one.pivots()
+        assert s1.size + a1.size > 0
+        assert all(np.array_equal(x, y) for x, y in zip(sum(p.pivots(), ()), sum(one.pivots(), ())))
+    finally:
+        one.close(); p.close()
+    X = sp.csc_matrix(scipy.linalg.block_diag(*[np.eye(70) * 70 + np.ones((70, 70))] * 2))
+    Ls = mex.symbchol(X)
+    assert Ls["xsuper"].size - 1 > 1
+    p = Plan(0)
+    try:
+        p.set_one_launch_fronts(False)
+        p.set_chol(Ls, X)
+        p.upload("ada", X.data)
+        p.blkchol_begin(pars, False)
+        with pytest.raises(SdmError, match="ONE dense front"):
+            p.blkchol_panels(0, 1, 0, 1, world=2, rank=0, blk=1)
+    finally:
+        p.close()
+
+
+def test_panel_record_refuses_a_panel_outside_the_front_before_launching():
+    """sdm_plan_panel_record checks the panel before k_panel_record reads or writes d, lb, the pivots and DT at its columns."""
+    from sedumi_amd.capi import SdmError
+    npanel = (200 + 63) // 64
+    p = _panel_plan(*_dense_front(200, 2))
+    try:
+        p.blkchol(None, False)
+        d0 = p.download("d")
+        p.kprof(True)
+        for panel in (-1, npanel):
+            for unpack in (False, True):
+                with pytest.raises(SdmError, match="0 <= panel < its panels"):
+                    p.panel_record(panel, unpack)
+        assert "k_panel_record" not in p.kprof_summary()
+        p.kprof(False)
+        assert np.array_equal(p.download("d"), d0)
+    finally:
+        p.close()
+
+
+def test_staged_factorisation_steps_need_a_begin():
+    """blkchol_levels / blkchol_panels / blkchol_end without a symbolic factor, or without a blkchol_begin before them (none yet, or the
+    last one already ended, or a new symbolic factor set since) raise instead of launching on whatever the plan holds."""
+    from sedumi_amd.capi import SdmError
+    from sedumi_amd.plan import Plan
+    front = _dense_front(130, 3)
+
+    def steps(p):
+        return lambda: p.blkchol_levels(0, 1), lambda: p.blkchol_panels(0, 1, 0, 1), p.blkchol_end
+    p = Plan(0)
+    try:
+        for step in steps(p):
+            with pytest.raises(SdmError, match="no symbolic factor"):
+                step()
+    finally:
+        p.close()
+    p, one = _panel_plan(*front), _panel_plan(*front)
+    try:
+        one.blkchol(None, False)
+        for before in ("nothing", "blkchol", "begin + set_chol"):
+            if before == "blkchol":
+                p.blkchol(None, False)
+            elif before == "begin + set_chol":
+                p.blkchol_begin(None, False)
+                p.set_chol(*front[:2])
+                p.upload("ada", front[2])
+            for step in steps(p):
+                with pytest.raises(SdmError, match="no factorisation begun"):
+                    step()
+        p.blkchol_begin(None, False)
+        p.blkchol_levels(0, 1)
+        p.blkchol_end()
+        assert np.array_equal(p.download("lpr"), one.download("lpr")) and np.array_equal(p.download("d"), one.download("d"))
+    finally:
+        p.close(); one.close()
+
+
 @pytest.mark.parametrize("ns,ms", [(4000, 4000), (1000, 1000), (900, 900), (960, 960), (1100, 1100), (1216, 1216), (700, 1500), (1300, 2100), (1024, 1030),
                                    (2050, 2050), (333, 2000), (64 * 9, 64 * 9 + 129), (64 * 9, 64 * 9 + 128), (2900, 3333)])
 def test_update_schedule_gives_every_tile_every_panel_once_and_in_order(ns, ms):

@@ -50,7 +50,7 @@ nrec = 4 * 64 + 2 + 64 * 64
 plans = []
 for r in range(world):
     p = bench.make_plan(0, P, L, ADA, Q, d, ud, rhs, qpr, one_launch_fronts=False)
-    p.set_column_owner(world, r, blk); p.upload("ada", vals); p.upload("absd", absd)
+    p.upload("ada", vals); p.upload("absd", absd)
     plans.append(p)
 buf = torch.zeros(plans[0].panel_slice(0)[1] + nrec, dtype=torch.float64, device=dev)
 best = None
@@ -59,7 +59,7 @@ for rep in range(3):
     t_begin = max(timed(p, lambda p=p: p.blkchol_begin(bench.PARS, True)) for p in plans)
     for q in range(npanel):
         for r, p in enumerate(plans):
-            launch[q, r] = timed(p, lambda p=p: p.blkchol_panels(0, 1, q, q + 1))
+            launch[q, r] = timed(p, lambda p=p: p.blkchol_panels(0, 1, q, q + 1, world, r, blk))
         src = (q // blk) % world
         off, n = plans[src].panel_slice(q)
         ps = plans[src]
