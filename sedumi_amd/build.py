@@ -64,7 +64,7 @@ def _compile_objects(extra, objdir, verbose):
     if verbose:
         for j in jobs:
             print(" ".join(j), flush=True)
-    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 1))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), int(os.environ.get("MAX_JOBS", 16))))) as ex:
         list(ex.map(subprocess.check_call, jobs))
     return hipcc, objs
 
@@ -114,7 +114,7 @@ def build_mexshims(lib=LIB, out=MEX_OUT, verbose=False):
     if verbose:
         for j in jobs:
             print(" ".join(j), flush=True)
-    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 1))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), int(os.environ.get("MAX_JOBS", 16))))) as ex:
         list(ex.map(subprocess.check_call, jobs))
     return out
 

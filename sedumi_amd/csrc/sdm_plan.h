@@ -432,9 +432,11 @@ struct PersistTurn {
 #endif
 };
 void set_error(const std::string &msg);
-// sdm_chol.hip
+// sdm_chol_build.hip
 void chol_build(sdm_plan *P, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const sdm_int *perm,
                 sdm_int nsuper, const sdm_int *xsuper, const sdm_int *ADAjc, const sdm_int *ADAir);
+// sdm_chol.hip
+int chol_front_wgs_per_cu();       // workgroups of k_ldl_front that fit one compute unit of the current device (chol_build; not in the emulator)
 void chol_factor(sdm_plan *P, const double canceltol, const double maxu, const double abstol, int use_absd);
 // the same in three steps (sdm_plan_blkchol_begin / _levels / _end: the multi-GPU layer reduces update matrices between levels)
 void chol_begin(sdm_plan *P, const double canceltol, const double maxu, const double abstol, int use_absd);

@@ -38,7 +38,7 @@ def _build(force=False):
         if force or not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_t):
             jobs.append(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-DSDM_EMU", "-x", "c++", "-I", HERE, "-I", CSRC,
                          "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-variable", "-c", s, "-o", o])
-    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 1))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), int(os.environ.get("MAX_JOBS", 16))))) as ex:
         list(ex.map(subprocess.check_call, jobs))
     subprocess.check_call(["g++", "-shared", "-o", LIB + ".tmp"] + objs)
     os.replace(LIB + ".tmp", LIB)                      # (never a half-written library under the name the tests load)

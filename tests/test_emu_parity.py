@@ -421,7 +421,7 @@ def test_one_launch_front_matches_the_panel_launches_bit_for_bit(refmex, m):
 @pytest.mark.parametrize("m", [330, 900, 1000])
 def test_streamed_update_tiles_give_the_same_bits_whatever_the_number_of_workgroups(refmex, m):
     """(m = 900, 15 tile rows: one deferred group whose far triangle goes in one launch; m = 1000, 16: two groups, the first one's far
-    triangle dealt over four launches -- tile_sched in sdm_chol.hip)"""
+    triangle dealt over four launches -- tile_sched in sdm_chol_sched.h)"""
     helpers.check_streamed_update_tiles(refmex, m)
 
 
@@ -694,7 +694,7 @@ def test_staged_factorisation_steps_need_a_begin():
 @pytest.mark.parametrize("ns,ms", [(4000, 4000), (1000, 1000), (900, 900), (960, 960), (1100, 1100), (1216, 1216), (700, 1500), (1300, 2100), (1024, 1030),
                                    (2050, 2050), (333, 2000), (64 * 9, 64 * 9 + 129), (64 * 9, 64 * 9 + 128), (2900, 3333)])
 def test_update_schedule_gives_every_tile_every_panel_once_and_in_order(ns, ms):
-    """tile_sched (sdm_chol.hip): the trailing updates of a big front on the launch-per-panel path -- eager tiles of the panel before, deferred
+    """tile_sched (sdm_chol_sched.h): the trailing updates of a big front on the launch-per-panel path -- eager tiles of the panel before, deferred
     macro tiles of whole groups of panels -- enumerated on the host for every panel launch (sdm_debug_tile_items) and replayed: every tile
     (I, J) of the front's lower triangle receives the panels 0 .. min(J, NP) - 1, each exactly once, in ascending order, never twice within a
     launch (two workgroups on one tile), and column q is complete but for panel q - 1 when launch q starts.  Fronts with rows beyond their
