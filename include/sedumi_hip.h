@@ -335,6 +335,29 @@ int sdm_plan_amul(sdm_plan *p, int transp);
 int sdm_plan_vecsym(sdm_plan *p);
 int sdm_plan_psdscale(sdm_plan *p, int transp, int use_perm);
 
+/* One whole normal-equations solve ADA' y = r: wrapPcg.m:43-130 with loopPcg.m:52-170 inside it, on the plan's stream
+ * (problems without dense columns).  Inputs: the resident scaling d of the last factor (buffers "dl", "ddet", "q1", "q2",
+ * "u" and the pivot order of sdm_plan_invcholfac), "qauxdet" / "qauxtr" (d.auxdet, d.auxtr as the caller's d holds them),
+ * DAt.q of sdm_plan_getdatq, "rv" (N) and, when use_rb != 0, "rb" (m).  restol = y0 * cg->restol.
+ * Outputs: plan buffers "pcg_y" (m), "pcg_dx" (N), "pcg_r" (m); *k = CG steps taken; info[SDM_WRAPPCG_INFO]:
+ *   info[0] refinement trials taken (cgpars.refine), info[1] STOP of the last loopPcg (0: none ran), info[2] loopPcg calls,
+ *   info[3] exit: 0 ssqrdx <= 0, 1 after the first step, 2 loopPcg returned no step, 3 norm(r,inf) < restol after a
+ *   loopPcg, 4 the refinement budget is spent.
+ * use_perm as in sdm_plan_psdscale.  Per CG step a few scalars come back to the host (one copy into pinned memory and a
+ * stream synchronise) to pick the next branch: the call synchronises and is NOT graph-capturable.  While the factor has
+ * blocks that iterative refinement of the solves may take (sdm_plan_set_refinement mode 1), a backward sweep also waits for
+ * the forward sweep before it, so that each solve refines exactly when a host loop's solve would.  Work vectors are
+ * allocated at the first call.  Refused, before any launch: no factor, no sdm_plan_set_ada, PSD blocks without "u",
+ * use_perm without a resident pivot order, dense columns (sdm_plan_pcg_init with nden > 0, or a resident dense-column
+ * factor). */
+typedef struct {
+  double restol, stagtol;   /* cgpars.restol (5e-3), cgpars.stagtol (5e-14) */
+  sdm_int maxiter, refine;  /* cgpars.maxiter (49), cgpars.refine (1) */
+  sdm_int qprec;            /* cgpars.qprec (1): double-double accumulation of y (quadadd) */
+} sdm_cgpars;
+#define SDM_WRAPPCG_INFO 4
+int sdm_plan_wrappcg(sdm_plan *p, const sdm_cgpars *cg, double y0, int use_rb, int use_perm, sdm_int *k, sdm_int *info);
+
 /* Make a factor computed elsewhere resident: Lpr[nnz(L)] on the pattern given to sdm_plan_set_chol, d[m] = L.d
  * (NULL: only the solves without ./d are meaningful).  No pivot report (skip / add) is attached to it. */
 int sdm_plan_load_factor(sdm_plan *p, const double *Lpr, const double *d);

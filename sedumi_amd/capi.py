@@ -29,6 +29,13 @@ class CholPars(C.Structure):
     _fields_ = [("canceltol", C.c_double), ("maxu", C.c_double), ("abstol", C.c_double)]
 
 
+class CgPars(C.Structure):
+    _fields_ = [("restol", C.c_double), ("stagtol", C.c_double), ("maxiter", C.c_int64), ("refine", C.c_int64), ("qprec", C.c_int64)]
+
+
+WRAPPCG_INFO = 4        # SDM_WRAPPCG_INFO
+
+
 class Cone(C.Structure):
     _fields_ = [("lpN", C.c_int64), ("lorN", C.c_int64), ("lorNL", I64P), ("sdpN", C.c_int64),
                 ("rsdpN", C.c_int64), ("sdpNL", I64P)]
@@ -62,6 +69,7 @@ def lib():
     L.sdm_plan_blkchol.argtypes = [C.c_void_p, C.POINTER(CholPars), C.c_int]
     L.sdm_plan_upload.argtypes = [C.c_void_p, C.c_char_p, F64P, C.c_int64]
     L.sdm_plan_download.argtypes = [C.c_void_p, C.c_char_p, F64P, C.c_int64]
+    L.sdm_plan_wrappcg.argtypes = [C.c_void_p, C.POINTER(CgPars), C.c_double, C.c_int, C.c_int, I64P, I64P]
     L.sdm_plan_timer_begin.argtypes = [C.c_void_p, C.c_int]
     L.sdm_plan_timer_end.argtypes = [C.c_void_p, C.c_int]
     L.sdm_plan_timer_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]

@@ -134,7 +134,18 @@ static DevBuf<double> *plan_buf(sdm_plan *p, const char *name) {
   if (s == "q2") return &p->ada.q2;
   if (s == "xN") { if (p->ada.xN.n == 0) throw std::runtime_error("buffer xN exists after the first sdm_plan_amul / vecsym / psdscale / pcg_init"); return &p->ada.xN; }
   if (s == "psd") { if (p->ada.psd.n == 0) throw std::runtime_error("buffer psd exists after sdm_plan_pcg_init"); return &p->ada.psd; }
-  if (s == "ad") return &p->dense.ad;       // dense columns Ad (m x nden, column major; deninfac.m:58-59)
+  // sdm_plan_wrappcg: inputs (allocated on first use) and outputs (allocated by its first call)
+  auto sized = [](DevBuf<double> &b, sdm_int n) -> DevBuf<double> * { if (b.n < (size_t)std::max<sdm_int>(n, 1)) b.alloc((size_t)std::max<sdm_int>(n, 1)); return &b; };
+  if (s == "rv") return sized(p->ada.wp_rv, p->ada.N);
+  if (s == "rb") return sized(p->ada.wp_rb, p->ada.m);
+  if (s == "qauxdet") return sized(p->ada.qauxdet, p->ada.lorN);
+  if (s == "qauxtr") return sized(p->ada.qauxtr, p->ada.lorN);
+  if (s == "pcg_y" || s == "pcg_dx" || s == "pcg_r") {
+    DevBuf<double> &b = s == "pcg_y" ? p->ada.wp_y : s == "pcg_dx" ? p->ada.wp_dx : p->ada.wp_r;
+    if (b.n == 0) throw std::runtime_error("buffer " + s + " exists after the first sdm_plan_wrappcg");
+    return &b;
+  }
+  if (s == "ad") return &p->dense.ad;      // dense columns Ad (m x nden, column major; deninfac.m:58-59)
   if (s == "lad") return &p->dense.lad;     // LAD = L \ Ad(perm,:) of the last sdm_plan_deninfac
   if (s == "dden") return &p->dense.dden;   // Ld of the last sdm_plan_deninfac
   // the arenas the multi-GPU layer exchanges slices of (sedumi_amd.dist.SeparatorShardedSolver)
@@ -437,6 +448,25 @@ int sdm_plan_psdscale(sdm_plan *p, int transp, int use_perm) {
   SDM_TRY
   if (!p->has_ada) throw std::runtime_error("sdm_plan_psdscale: no problem data set (sdm_plan_set_ada)");
   pcg_psdscale(p, transp, use_perm != 0);
+  SDM_CATCH
+}
+int sdm_plan_wrappcg(sdm_plan *p, const sdm_cgpars *cg, double y0, int use_rb, int use_perm, sdm_int *k, sdm_int *info) {
+  SDM_TRY
+  // every refusal before the first launch
+  if (!cg) throw std::runtime_error("sdm_plan_wrappcg: no cgpars");
+  if (!p->has_ada) throw std::runtime_error("sdm_plan_wrappcg: no problem data set (sdm_plan_set_ada)");
+  if (!p->factored) throw std::runtime_error("sdm_plan_wrappcg: no factor resident");
+  if (p->capturing) throw std::runtime_error("sdm_plan_wrappcg synchronises once per CG step: not inside a graph capture");
+  if (p->ada.aden_n > 0 || p->dense.factored) throw std::runtime_error("sdm_plan_wrappcg: dense columns are not supported (sdm_plan_pcg_init with nden > 0 or a resident dense-column factor)");
+  if (p->ada.lenud > 0 && p->ada.ufac.n < (size_t)p->ada.lenud) throw std::runtime_error("sdm_plan_wrappcg: PSD blocks need the scaling's \"u\" (upload it first)");
+  if (use_perm && !p->ada.ic_has_perm) throw std::runtime_error("sdm_plan_wrappcg: use_perm without a resident pivot order (sdm_plan_invcholfac with perm)");
+  if (p->ada.wp_rv.n < (size_t)std::max<sdm_int>(p->ada.N, 1)) throw std::runtime_error("sdm_plan_wrappcg: upload buffer \"rv\" first");
+  if (use_rb && p->ada.wp_rb.n < (size_t)std::max<sdm_int>(p->ada.m, 1)) throw std::runtime_error("sdm_plan_wrappcg: upload buffer \"rb\" first (or use_rb = 0)");
+  if (p->ada.lorN > 0 && (p->ada.qauxdet.n < (size_t)p->ada.lorN || p->ada.qauxtr.n < (size_t)p->ada.lorN))
+    throw std::runtime_error("sdm_plan_wrappcg: Lorentz cones need \"qauxdet\" and \"qauxtr\" (d.auxdet, d.auxtr)");
+  SDM_HIP_CHECK(hipSetDevice(p->device));
+  pcg_wrap(p, cg, y0, use_rb != 0, use_perm != 0, k, info);
+  check_plan_health(p);
   SDM_CATCH
 }
 // ---- resident dense-column unit (deninfac.m:58-94)

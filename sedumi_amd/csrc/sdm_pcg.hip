@@ -169,7 +169,7 @@ k_psdscale(double *out, const double *in, const double *u, PsdBlk B, const int *
 }
 
 // =========================================================================== host
-static void pcg_prepare(sdm_plan *P) {
+void pcg_prepare(sdm_plan *P) {
   AdaPlan &A = P->ada;
   if (A.pcg_ready) return;
   if (A.h_Ajc.empty()) throw std::runtime_error("Amul / psdscale / vecsym need the problem data of sdm_plan_set_ada");
@@ -206,14 +206,19 @@ static void pcg_prepare(sdm_plan *P) {
 
 void pcg_amul(sdm_plan *P, int transp) {
   pcg_prepare(P);
+  pcg_amul_on(P, transp, transp ? P->y.p : P->ada.xN.p, transp ? P->ada.xN.p : P->rhs.p);
+}
+// the same between explicit device vectors: transp = 0  out[m] = At' in[N] ; transp = 1  out[N] = At in[m]
+void pcg_amul_on(sdm_plan *P, int transp, const double *in, double *out) {
+  pcg_prepare(P);
   AdaPlan &A = P->ada;
   const int m = (int)A.m;
   if (!transp) {
-    SDM_KLAUNCH(P, k_amul_cols, dim3(std::max(1, std::min(1024, (m + 3) / 4))), dim3(256), 0, P->rhs.p, A.xN.p, A.d_Ajc.p, A.d_Air.p, A.d_Apr.p, m);
-    if (A.aden_n > 0) SDM_KLAUNCH(P, k_amul_dense, dim3((m + 255) / 256), dim3(256), 0, P->rhs.p, A.xN.p, A.aden.p, A.aden_cols.p, m, A.aden_n, 0);
+    SDM_KLAUNCH(P, k_amul_cols, dim3(std::max(1, std::min(1024, (m + 3) / 4))), dim3(256), 0, out, in, A.d_Ajc.p, A.d_Air.p, A.d_Apr.p, m);
+    if (A.aden_n > 0) SDM_KLAUNCH(P, k_amul_dense, dim3((m + 255) / 256), dim3(256), 0, out, const_cast<double *>(in), A.aden.p, A.aden_cols.p, m, A.aden_n, 0);
   } else {
-    SDM_KLAUNCH(P, k_amul_rows, dim3((unsigned)((A.N + 255) / 256)), dim3(256), 0, A.xN.p, P->y.p, A.d_Tjc.p, A.d_Tir.p, A.d_Tpr.p, (int64_t)A.N);
-    if (A.aden_n > 0) SDM_KLAUNCH(P, k_amul_dense, dim3(A.aden_n), dim3(256), 0, P->y.p, A.xN.p, A.aden.p, A.aden_cols.p, m, A.aden_n, 1);
+    SDM_KLAUNCH(P, k_amul_rows, dim3((unsigned)((A.N + 255) / 256)), dim3(256), 0, out, in, A.d_Tjc.p, A.d_Tir.p, A.d_Tpr.p, (int64_t)A.N);
+    if (A.aden_n > 0) SDM_KLAUNCH(P, k_amul_dense, dim3(A.aden_n), dim3(256), 0, const_cast<double *>(in), out, A.aden.p, A.aden_cols.p, m, A.aden_n, 1);
   }
 }
 
@@ -230,27 +235,36 @@ void pcg_set_dense(sdm_plan *P, sdm_int nden, const sdm_int *cols, const double 
 
 void pcg_vecsym(sdm_plan *P) {
   pcg_prepare(P);
+  pcg_vecsym_on(P, P->ada.xN.p);
+}
+// x: a cone-space vector (N doubles) on the device, its PSD part symmetrised in place
+void pcg_vecsym_on(sdm_plan *P, double *x) {
+  pcg_prepare(P);
   AdaPlan &A = P->ada;
   const int nb = (int)A.psd_n.size();
   if (nb == 0) return;
   const int64_t base = A.N - A.lenud;                               // PSD part = the tail of a cone-space vector
-  SDM_KLAUNCH(P, k_vecsym, dim3(64, nb), dim3(256), 0, A.xN.p + base, A.pb_n.p, A.pb_off.p, A.pb_herm.p, nb);
+  SDM_KLAUNCH(P, k_vecsym, dim3(64, nb), dim3(256), 0, x + base, A.pb_n.p, A.pb_off.p, A.pb_herm.p, nb);
 }
 
 // perm: device int32, per block concatenated, 0-based (the one sdm_plan_invcholfac uploaded) or null
 void pcg_psdscale(sdm_plan *P, int transp, bool with_perm) {
+  pcg_prepare(P);
+  pcg_psdscale_on(P, transp, with_perm, P->ada.xN.p + (P->ada.N - P->ada.lenud), P->ada.psd.p);
+}
+// in, out: PSD parts (lenud doubles) on the device, out != in
+void pcg_psdscale_on(sdm_plan *P, int transp, bool with_perm, const double *in, double *out) {
   pcg_prepare(P);
   AdaPlan &A = P->ada;
   if (A.pcg_ntiles == 0) return;
   if (A.ufac.n < (size_t)A.lenud) throw std::runtime_error("psdscale: upload buffer \"u\" (d.u) first");
   if (with_perm && !A.ic_has_perm) throw std::runtime_error("psdscale: no pivot order resident (sdm_plan_invcholfac with perm uploads it)");
   PsdBlk B; B.n = A.pb_n.p; B.off = A.pb_off.p; B.herm = A.pb_herm.p; B.poff = A.pb_poff.p;
-  const int64_t base = A.N - A.lenud;
   const int *perm = with_perm ? A.ic_perm.p : nullptr;
   // prep = ~transp (the pivot order on the way in), postp = transp (on the way out)   psdscale.m:67-69
-  SDM_KLAUNCH(P, k_psdscale<1>, dim3(A.pcg_ntiles), dim3(PT), 0, A.psdtmp.p, A.xN.p + base, A.ufac.p, B, A.pb_items.p, perm, transp,
+  SDM_KLAUNCH(P, k_psdscale<1>, dim3(A.pcg_ntiles), dim3(PT), 0, A.psdtmp.p, in, A.ufac.p, B, A.pb_items.p, perm, transp,
               (with_perm && !transp) ? 1 : 0);
-  SDM_KLAUNCH(P, k_psdscale<2>, dim3(A.pcg_ntiles), dim3(PT), 0, A.psd.p, A.psdtmp.p, A.ufac.p, B, A.pb_items.p, perm, transp,
+  SDM_KLAUNCH(P, k_psdscale<2>, dim3(A.pcg_ntiles), dim3(PT), 0, out, A.psdtmp.p, A.ufac.p, B, A.pb_items.p, perm, transp,
               (with_perm && transp) ? 1 : 0);
 }
 

@@ -298,6 +298,11 @@ struct AdaPlan {
   DevBuf<int64_t> d_Tjc, pb_off; DevBuf<int> d_Tir, pb_n, pb_herm, pb_poff, pb_items, aden_cols;
   DevBuf<double> d_Tpr, xN, psd, psdtmp, aden;
   int pcg_ntiles = 0, aden_n = 0;
+  // ---- sdm_plan_wrappcg (sdm_wrappcg.hip): inputs "rv" (N), "rb" (m), "qauxdet" / "qauxtr" (d.auxdet, d.auxtr: lorN); outputs
+  // "pcg_y" (m), "pcg_dx" (N), "pcg_r" (m); one arena of work vectors, the per-workgroup partials and the scalars of the
+  // loop (allocated at the first call), their pinned host copy
+  DevBuf<double> wp_rv, wp_rb, qauxdet, qauxtr, wp_y, wp_dx, wp_r, wp_work, wp_part, wp_sc;
+  PinnedInts wp_host;
   size_t stage1_lds = 0;
   // stage-2 fast path: interleaved (ELL) copy of the PSD nonzeros, rows sorted by length, groups of 64
   bool ell_ok = false;
@@ -470,6 +475,13 @@ void pcg_amul(sdm_plan *P, int transp);
 void pcg_set_dense(sdm_plan *P, sdm_int nden, const sdm_int *cols, const double *Aden);
 void pcg_vecsym(sdm_plan *P);
 void pcg_psdscale(sdm_plan *P, int transp, bool with_perm);
+// the same three on explicit device vectors (sdm_wrappcg.hip); pcg_prepare builds the tables on first use
+void pcg_prepare(sdm_plan *P);
+void pcg_amul_on(sdm_plan *P, int transp, const double *in, double *out);
+void pcg_vecsym_on(sdm_plan *P, double *x);
+void pcg_psdscale_on(sdm_plan *P, int transp, bool with_perm, const double *in, double *out);
+// sdm_wrappcg.hip: wrapPcg.m / loopPcg.m as one call (sdm_plan_wrappcg)
+void pcg_wrap(sdm_plan *P, const sdm_cgpars *cg, double y0, bool use_rb, bool use_perm, sdm_int *k, sdm_int *info);
 // sdm_dpr1.hip: resident dense-column unit (deninfac.m:58-94)
 void dense_set(sdm_plan *P, sdm_int nden, const sdm_int *LADjc, const sdm_int *LADir, const sdm_int *dzjc, const sdm_int *dzir,
                const sdm_int *colperm, const sdm_int *first);

@@ -184,9 +184,11 @@ class PlanHot:
     per iteration the loop uploads d.{l,det,q1,q2,u} (+ d.perm), and per solve one right-hand side."""
     name = "sedumi_amd.plan"
 
-    def __init__(self, device=0, device_ops=True):
+    def __init__(self, device=0, device_ops=True, device_pcg=False):
+        """device_pcg: every wrapPcg (no dense columns) as ONE call of the library (Plan.wrappcg), off by default"""
         self.device, self.plan = device, None
         self._pcg, self._d, self._want_ops = False, None, device_ops
+        self.device_pcg = bool(device_pcg) and device_ops
 
     def factor(self, S, d, DAt, L, pars, den=None):
         from sedumi_amd.plan import Plan
@@ -209,6 +211,8 @@ class PlanHot:
         if K["q"].size:
             pl.upload("q1", d["q1"]); pl.upload("q2", d["q2"])
             pl.getdatq()                                            # getDAtm.m:39-44
+            if self.device_pcg:                                     # asmDxq.m reads them as updtransfo.m made them
+                pl.upload("qauxdet", d["auxdet"]); pl.upload("qauxtr", d["auxtr"])
         if np.sum(K["s"]) > 0:
             pl.upload("u", d["u"])
             pl.invcholfac(d["perm"] if np.size(d["perm"]) else None)   # sedumi.m:452
@@ -266,6 +270,11 @@ class PlanHot:
         pl = self.plan
         pl.upload("y", vec(p)); pl.amul(1); pl.vecsym()
         return pl.download("xN", self._N)
+
+    def wrapPcg(self, d, rb, rv, cgpars, y0):
+        """wrapPcg.m with loopPcg.m as one device call (sdm_plan_wrappcg) on the d of the last factor()"""
+        y, dx, k, r, self.last_pcg_info = self.plan.wrappcg(rv, rb, y0, cgpars, bool(np.size(d["perm"])))
+        return y, dx, k, r
 
     def psdscale(self, d, x, transp):
         """psdscale(d, x, K[, transp]) with the d of the last factor() (its d.u and pivot order are resident)"""
@@ -594,19 +603,32 @@ class Sedumi:
     def bwsolve(self, L, yv):
         return vec(self.hot.bw(L, self.hot.bwdpr1(L, yv)))         # wrapPcg.m:59  sparbwslv(L, bwdpr1(Lden, y))
 
+    # inner products of wrapPcg / loopPcg / PopK (a test swaps them for extended-precision ones)
+    @staticmethod
+    def _dot(a, b):
+        return a @ b
+
+    @staticmethod
+    def _sum(v):
+        return np.sum(v)
+
     def wrapPcg(self, L, d, DAt, rb, rv, cgpars, y0):
+        h = self._ops(d)
+        if h is not None and getattr(h, "device_pcg", False):          # the whole solve as one library call (PlanHot(device_pcg=True))
+            return h.wrapPcg(d, rb, rv, cgpars, y0)
         cn = self.cone
+        self.pcg_info = {"trials": 0, "stop": 0}
         restol = y0 * cgpars["restol"]
         dx = self.Dx(d, rv, True)
         r = self.Amul(dx)
         if rb is not None:
             r = r + rb
         p, yv = self.precond(L, r)
-        ssqrNew = p @ yv
+        ssqrNew = self._dot(p, yv)
         p = self.bwsolve(L, yv)
         x = self.Amul1_vecsym(p)
         dx = self.Dx(d, x, False)
-        ssqrdx = dx @ dx
+        ssqrdx = self._dot(dx, dx)
         if ssqrdx <= 0.0:
             return np.zeros(r.size), rv.copy(), 0, r
         k = 1
@@ -622,6 +644,7 @@ class Sedumi:
         trial = 0
         pcur = p
         while True:
+            self.pcg_info["trials"] = trial
             dy, dk, xx = self.loopPcg(L, d, DAt, r, pcur, ssqrNew, cgpars, restol)
             if dy is None:
                 return y, dx, k, r
@@ -644,7 +667,7 @@ class Sedumi:
         ddotx = d["q1"] * x[i1:i2] + cn.ddot(d["q2"], x)
         Dxp = self.psdscale(d, x)
         y = np.concatenate((y, self.psdscale(d, Dxp, True)))
-        xTy = x[:cn.lq] @ y[:cn.lq] + np.sum(ddotx ** 2) + np.sum(Dxp ** 2)
+        xTy = self._dot(x[:cn.lq], y[:cn.lq]) + self._sum(ddotx ** 2) + self._sum(Dxp ** 2)
         return y, ddotx, Dxp, xTy
 
     def loopPcg(self, L, d, DAt, b, p, ssqrNew, cgpars, restol):
@@ -660,11 +683,11 @@ class Sedumi:
         while STOP == 0:
             Lr, tmp = self.precond(L, r)
             if p is None:
-                ssqrNew = Lr @ tmp
+                ssqrNew = self._dot(Lr, tmp)
                 p = self.bwsolve(L, tmp)
             else:
                 ssqrOld = ssqrNew
-                ssqrNew = Lr @ tmp
+                ssqrNew = self._dot(Lr, tmp)
                 p = (ssqrNew / ssqrOld) * p
                 p = p + self.bwsolve(L, tmp)
             Ap = self.Amul1_vecsym(p)
@@ -672,15 +695,17 @@ class Sedumi:
             if ssqrDAp > 0.0:
                 k += 1
                 alpha = ssqrNew / ssqrDAp
-                if y is not None:
+                if y is not None and y[1] is None:                  # cg.qprec == 0
+                    y = (y[0] + alpha * p, None)
+                elif y is not None:
                     hi, lo = self.ref.call("quadadd", 2, col(y[0]), col(y[1]), col(alpha * p))
                     y = (vec(hi), vec(lo))
                 else:
-                    y = (alpha * p, np.zeros(p.size))              # cg.qprec > 0
+                    y = (alpha * p, np.zeros(p.size) if cgpars["qprec"] > 0 else None)
                 tmpv = self.Amul(DDAp) + (vec(sp.csc_matrix(DAt["q"]).T @ DApq) if cn.nq else 0.0)
                 r = r - alpha * tmpv
                 fiprev = finew
-                finew = (b + r) @ y[0] + (b + r) @ y[1]
+                finew = self._dot(b + r, y[0]) + self._dot(b + r, y[1]) if y[1] is not None else self._dot(b + r, y[0])
                 normr = np.abs(r).max()
                 if normr < normrmin:
                     ymin = y
@@ -693,6 +718,7 @@ class Sedumi:
                     STOP = 2
             else:
                 STOP = 1
+        self.pcg_info["stop"] = STOP
         if STOP == 2:
             y = ymin
         if y is None:
@@ -701,7 +727,7 @@ class Sedumi:
             DAy = alpha * np.concatenate((np.sqrt(d["l"]) * Ap[:cn.l], cn.asmDxq(d, Ap, DApq), DAps))
         else:
             DAy = 0.0
-            for part in y:
+            for part in (v for v in y if v is not None):
                 Ap2 = self.Amul1_vecsym(part)
                 DAy = DAy + self.Dx(d, Ap2, False)
         return y[0], k, DAy

@@ -144,6 +144,23 @@ class Plan:
     def psdscale(self, transp=0, use_perm=False):
         check(self._lib.sdm_plan_psdscale(C.c_void_p(self._p), int(transp), 1 if use_perm else 0))
 
+    def wrappcg(self, rv, rb, y0, cg, use_perm=False):
+        """[y, dx, k, r] = wrapPcg(L, Lden, At, dense, d, DAt, K, rb, rv, cgpars, y0) (wrapPcg.m with loopPcg.m, no dense columns) as ONE
+        device call on the resident factor and scaling (d.auxdet / d.auxtr in "qauxdet" / "qauxtr" when there are Lorentz cones).
+        rb None: no rb.  cg: the cgpars dict (restol, stagtol, maxiter, refine, qprec).  Returns (y, dx, k, r, info) with
+        info = {"trials", "stop", "loops", "exit"} (include/sedumi_hip.h: sdm_plan_wrappcg)."""
+        rv = f64(rv)
+        self.upload("rv", rv)
+        if rb is not None:
+            self.upload("rb", rb)
+        cp = capi.CgPars(float(cg["restol"]), float(cg["stagtol"]), int(cg["maxiter"]), int(cg["refine"]), int(cg["qprec"]))
+        k = np.zeros(1, dtype=np.int64)
+        info = np.zeros(capi.WRAPPCG_INFO, dtype=np.int64)
+        check(self._lib.sdm_plan_wrappcg(C.c_void_p(self._p), C.byref(cp), C.c_double(float(y0)), 0 if rb is None else 1, 1 if use_perm else 0,
+                                         pi(k), pi(info)))
+        y, dx, r = self.download("pcg_y", self.m), self.download("pcg_dx", rv.size), self.download("pcg_r", self.m)
+        return y, dx, int(k[0]), r, {"trials": int(info[0]), "stop": int(info[1]), "loops": int(info[2]), "exit": int(info[3])}
+
     def load_factor(self, LL, Ld=None):
         """Make an externally computed factor resident: L.L values on the plan's pattern and L.d."""
         LL = sp.csc_matrix(LL); LL.sort_indices()
