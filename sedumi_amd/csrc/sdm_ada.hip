@@ -715,8 +715,10 @@ k_psd_stage1(Stage1Tab T, const double *udsqr, double *zbuf, int ldsY, int task0
 // n x n x nslot GEMM (Y = D X(:,cols) as above), accumulated over chunks of S1_KC slots; every wavefront owns a
 // fixed set of 16x16 tiles of Z in registers.  The targets are read off the finished Z in LDS:
 // z(r,c) = (Z[r][c] + Z[c][r]) / 2  -- the same two sums as spscale.c:283-304.
-__global__ void __launch_bounds__(64 * S1_WAVES, 4)
-k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int task0, const int *order, double *zero_ptr, long long zero_n) {
+// Three tasks per compute unit at np = 80 (blocks of order 65 .. 80): at most 80 vector registers, and LDS = ldsY doubles
+// (Yl / Dl, later Zl) + nzcap nonzeros + the slot table <= 163 840 / 3 bytes (tests/test_stage1_mfma.py reads both off the code object).
+__global__ void __launch_bounds__(64 * S1_WAVES, 3 * S1_WAVES / 4)
+k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int ldsY, int nzcap, int task0, const int *order, double *zero_ptr, long long zero_n) {
   SDM_DYN_SMEM(smem);
   // (a zero LP / Lorentz part of ADA': cleared here, by everybody a slice, instead of by a memset launch of its own in front of
   // this one -- stage 2, the first reader, is a launch later)
@@ -726,8 +728,8 @@ k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int task0, con
   const int np = (n + 15) & ~15, nt = np >> 4, ntile = nt * nt;
   double *Yl = (double *)smem;                      // Yl[t*np + i], t < S1_KC
   double *Dl = Yl + S1_KC * np;                     // Dl[t*np + j] = D[col_t][j]
-  double *Zl = (double *)smem;                      // Zl[i*np + j]: written after the last GEMM chunk, aliases Yl/Dl
-                                                    // (LDS per task = max(2*16*np, np*np) doubles -> several tasks per CU)
+  double *Zl = (double *)smem;                      // Zl[i*ldz + j], i, j < n: written after the last GEMM chunk, aliases Yl/Dl
+  const int ldz = n | 1;                            // (odd: the targets read Z down a column as well as along a row)
   const int64_t slot0 = T.t_slotptr[task], tend = T.t_end[task];
   const double *D = udsqr + T.t_udoff[task];
   double *z = zbuf + T.t_zoff[task];
@@ -735,15 +737,19 @@ k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int task0, con
   const int tid = threadIdx.x, bs = blockDim.x;
   const int wave = SDM_UNIFORM_INT(tid >> 6), lane = tid & 63, nw = bs >> 6;      // (the wavefront index in a scalar register)
   const int li = lane & 15, lk = lane >> 4;
+  const int rcpn = ((1 << 20) + n - 1) / n;         // ceil(2^20 / n): e / n as a multiplication in the Y loop
+  static_assert(S1_KC * S1_MAXN * S1_MAXN < (1 << 20) && S1_KC % 4 == 0, "k_psd_stage1_mfma: reciprocal division, four slots per MFMA step");
   sdm_double4 acc[S1_MAXT];
   for (int x = 0; x < S1_MAXT; x++) for (int r = 0; r < 4; r++) acc[x][r] = 0.0;
-  __shared__ double nzx[S1_NZ];                     // the task's nonzeros: value ...
-  __shared__ int nzr[S1_NZ];                        // ... and row offset inside the block
+  // the task's nonzeros (value, row offset inside the block) behind the Y / D-row area: nzcap of them, sized by the launch for
+  // its largest task (<= S1_NZ) -- as static arrays of S1_NZ they were 18 KB of every task's LDS
+  double *nzx = (double *)smem + ldsY;
+  int *nzr = (int *)(nzx + nzcap);
   __shared__ int sbeg[S1_MAXN + 1], scol[S1_MAXN];  // slot -> first nonzero (relative), column of X_jk
   SDM_PHASE_BEGIN();
   // ONE round trip brings the whole task (nonzeros + slot table) into LDS: every later load of D depends on LDS only
   const int64_t nzb = T.s_nzptr[slot0];
-  const bool staged = tend - nzb <= S1_NZ && nslot <= S1_MAXN;
+  const bool staged = tend - nzb <= nzcap && nslot <= S1_MAXN;
   if (staged) {
     for (int64_t u = nzb + tid; u < tend; u += bs) { nzx[u - nzb] = T.Apr[u]; nzr[u - nzb] = (int)(T.Air[u] - rowbase); }
     for (int t = tid; t <= nslot; t += bs) sbeg[t] = (int)((t < nslot ? T.s_nzptr[slot0 + t] : tend) - nzb);
@@ -751,39 +757,42 @@ k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int task0, con
   }
   __syncthreads();
   SDM_PHASE(0);
+  // zeros in the padding columns [n, np) of all rows, once: the chunks write the columns below n only, and Z takes the area over
+  // behind the last chunk
+  for (int t = wave; t < S1_KC; t += nw)
+    if (lane < np - n) { Yl[t * np + n + lane] = 0.0; Dl[t * np + n + lane] = 0.0; }
   for (int c0 = 0; c0 < nslot; c0 += S1_KC) {
-    const int cc = min(S1_KC, nslot - c0);
-    for (int t = wave; t < S1_KC; t += nw) {
-      if (t < cc) {
-        int sb, se, col;
-        if (staged) { sb = sbeg[c0 + t]; se = sbeg[c0 + t + 1]; col = scol[c0 + t]; }
-        else {
-          sb = (int)(T.s_nzptr[slot0 + c0 + t] - nzb);
-          se = (int)(((c0 + t + 1 < nslot) ? T.s_nzptr[slot0 + c0 + t + 1] : tend) - nzb);
-          col = T.s_col[slot0 + c0 + t];
-        }
-        for (int i = lane; i < np; i += 64) {
-          double a = 0.0;
-          if (i < n) {
-            if (staged) {
-              int u = sb;
-              for (; u + 4 <= se; u += 4) {               // 4 independent column loads of D in flight
-                const double d0 = D[(int64_t)(nzr[u] - col * n) * n + i], d1 = D[(int64_t)(nzr[u + 1] - col * n) * n + i];
-                const double d2 = D[(int64_t)(nzr[u + 2] - col * n) * n + i], d3 = D[(int64_t)(nzr[u + 3] - col * n) * n + i];
-                a += nzx[u] * d0; a += nzx[u + 1] * d1; a += nzx[u + 2] * d2; a += nzx[u + 3] * d3;
-              }
-              for (; u < se; u++) a += nzx[u] * D[(int64_t)(nzr[u] - col * n) * n + i];
-            } else {
-              for (int64_t u = nzb + sb; u < nzb + se; u++) a += T.Apr[u] * D[(int64_t)((int)(T.Air[u] - rowbase) - col * n) * n + i];
-            }
-          }
-          Yl[t * np + i] = a;
-          Dl[t * np + i] = i < n ? D[(int64_t)col * n + i] : 0.0;
-        }
-      } else {
-        for (int i = lane; i < np; i += 64) { Yl[t * np + i] = 0.0; Dl[t * np + i] = 0.0; }
+    const int cc = min(S1_KC, nslot - c0), kq = (cc + 3) & ~3;    // an MFMA step takes four slots: only the steps that hold one are run
+    // Y and the slots' rows of D: the cc x n entries dealt over the whole workgroup (a wavefront per slot made a second, nearly empty
+    // trip for the rows beyond 64 of a block of order 70, behind the same chain of dependent loads); per entry the sum runs over the
+    // slot's nonzeros in stored order
+    for (int e = tid; e < cc * n; e += bs) {
+      const int t = (e * rcpn) >> 20, i = e - t * n;             // e / n: exact while e * (rcpn * n - 2^20) < 2^20, and e < S1_KC * n, rcpn * n - 2^20 < n
+      int sb, se, col;
+      if (staged) { sb = sbeg[c0 + t]; se = sbeg[c0 + t + 1]; col = scol[c0 + t]; }
+      else {
+        sb = (int)(T.s_nzptr[slot0 + c0 + t] - nzb);
+        se = (int)(((c0 + t + 1 < nslot) ? T.s_nzptr[slot0 + c0 + t + 1] : tend) - nzb);
+        col = T.s_col[slot0 + c0 + t];
       }
+      double a = 0.0;
+      if (staged) {
+        int u = sb;
+        for (; u + 4 <= se; u += 4) {               // 4 independent column loads of D in flight
+          const double d0 = D[(int64_t)(nzr[u] - col * n) * n + i], d1 = D[(int64_t)(nzr[u + 1] - col * n) * n + i];
+          const double d2 = D[(int64_t)(nzr[u + 2] - col * n) * n + i], d3 = D[(int64_t)(nzr[u + 3] - col * n) * n + i];
+          a += nzx[u] * d0; a += nzx[u + 1] * d1; a += nzx[u + 2] * d2; a += nzx[u + 3] * d3;
+        }
+        for (; u < se; u++) a += nzx[u] * D[(int64_t)(nzr[u] - col * n) * n + i];
+      } else {
+        for (int64_t u = nzb + sb; u < nzb + se; u++) a += T.Apr[u] * D[(int64_t)((int)(T.Air[u] - rowbase) - col * n) * n + i];
+      }
+      Yl[t * np + i] = a;
+      Dl[t * np + i] = D[(int64_t)col * n + i];
     }
+    // zeros in the rows [cc, kq) the last MFMA step reads beyond the slots
+    for (int t = cc + wave; t < kq; t += nw)
+      for (int i = lane; i < n; i += 64) { Yl[t * np + i] = 0.0; Dl[t * np + i] = 0.0; }
     SDM_PHASE(1);
     __syncthreads();
     SDM_PHASE(2);
@@ -791,12 +800,19 @@ k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int task0, con
       const int tile = wave + x * nw;
       if (tile < ntile) {                               // wave-uniform
         const int I = tile / nt, J = tile - I * nt;
-#pragma unroll 4
-        for (int q = 0; q < S1_KC / 4; q++) {
-          const double a = Yl[(4 * q + lk) * np + I * 16 + li];
-          const double b = Dl[(4 * q + lk) * np + J * 16 + li];
-          acc[x] = SDM_MFMA_F64_16x16x4(a, b, acc[x]);
+        // (the pitch made opaque: the operand addresses are formed here, per tile and chunk -- hoisted out of the chunk loop, those of all
+        // tiles' unrolled steps were 32 registers more than three tasks per compute unit leave a work-item)
+        int npo = np; SDM_PIN(npo);
+        const double *Ya = Yl + lk * npo + I * 16 + li, *Db = Dl + lk * npo + J * 16 + li;
+        int q = 0;
+        for (; q + 4 <= kq / 4; q += 4) {                 // the operands of four steps in flight
+          double a[4], b[4];
+#pragma unroll
+          for (int k = 0; k < 4; k++) { a[k] = Ya[4 * (q + k) * npo]; b[k] = Db[4 * (q + k) * npo]; }
+#pragma unroll
+          for (int k = 0; k < 4; k++) acc[x] = SDM_MFMA_F64_16x16x4(a[k], b[k], acc[x]);
         }
+        for (; q < kq / 4; q++) acc[x] = SDM_MFMA_F64_16x16x4(Ya[4 * q * npo], Db[4 * q * npo], acc[x]);
       }
     }
     SDM_PHASE(3);
@@ -807,7 +823,8 @@ k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int task0, con
     const int tile = wave + x * nw;
     if (tile < ntile) {
       const int I = tile / nt, J = tile - I * nt;
-      for (int r = 0; r < 4; r++) Zl[(I * 16 + lk + 4 * r) * np + J * 16 + li] = acc[x][r];
+      for (int r = 0; r < 4; r++)
+        if (I * 16 + lk + 4 * r < n && J * 16 + li < n) Zl[(I * 16 + lk + 4 * r) * ldz + J * 16 + li] = acc[x][r];
     }
   }
   __syncthreads();
@@ -823,7 +840,7 @@ k_psd_stage1_mfma(Stage1Tab T, const double *udsqr, double *zbuf, int task0, con
     for (int x = 0; x < 8; x++) {
       const int u = u0 + x * bs + tid;
       const int r = rc[x] >> 16, c = rc[x] & 0xffff;
-      if (u < ulen) z[u] = (Zl[r * np + c] + Zl[c * np + r]) / 2;
+      if (u < ulen) z[u] = (Zl[r * ldz + c] + Zl[c * ldz + r]) / 2;
     }
   }
   SDM_PHASE(6);
@@ -1446,16 +1463,19 @@ void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, boo
 #ifndef SDM_EMU
     SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_psd_stage1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)A.stage1_lds));
 #endif
+    const int nzcap = s1_nzcap(A.s1_maxnz);
     if (A.maxn <= S1_MAXN && A.sdpN == A.rsdpN) {
-      const int np = (A.maxn + 15) & ~15;
-      const size_t lds = (size_t)std::max(2 * S1_KC * np, np * np) * sizeof(double);
+      // LDS per task: Yl and Dl of a chunk (S1_KC slots x np), under them the finished Z (n x (n | 1)); behind them the nonzeros of the
+      // plan's largest task.  At maxn = 70 that is 40 960 + 7 584 bytes (+ the kernel's static slot table): three tasks per compute unit
+      const int ldsy = s1_mfma_ldsy(A.maxn);
+      const size_t lds = s1_mfma_lds(A.maxn, A.s1_maxnz);
 #ifndef SDM_EMU
       if (lds > 48 * 1024) SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_psd_stage1_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 #endif
       double *zp = A.zero_ptr; const long long zn = A.zero_n;         // (taken over from ada_lq: see ada_zero_flush)
       A.zero_ptr = nullptr; A.zero_n = 0;
       stage1_cleared_all = zp == ada + P->ada_jc[A.col0] && zn == (long long)(P->ada_jc[A.col1] - P->ada_jc[A.col0]);
-      SDM_KLAUNCH(P, k_psd_stage1_mfma, dim3((unsigned)ntask), dim3(64 * S1_WAVES), lds, T, A.udsqr.p, A.zbuf.p, task0,
+      SDM_KLAUNCH(P, k_psd_stage1_mfma, dim3((unsigned)ntask), dim3(64 * S1_WAVES), lds, T, A.udsqr.p, A.zbuf.p, ldsy, nzcap, task0,
                   (ntask == (int)A.ntask) ? (const int *)A.t_order.p : (const int *)nullptr, zp, zn);
     } else
     {
@@ -1463,7 +1483,6 @@ void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, boo
       // hide each other's latencies better than one task with all its slots resident
       const size_t one = (size_t)(A.sdpN > A.rsdpN ? 4 : 2) * (size_t)A.maxn * sizeof(double);
       const size_t ldsy = std::max(one, std::min(A.stage1_lds, (size_t)S1_GEN_LDS));
-      const int nzcap = (int)std::min<int64_t>(S1_NZ, (A.s1_maxnz + 1) & ~(int64_t)1);
       const size_t lds = ldsy + (size_t)nzcap * (sizeof(double) + sizeof(int));
 #ifndef SDM_EMU
       SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_psd_stage1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -12,9 +12,14 @@ constexpr int NB = 64;     // factor panel width (columns)
 constexpr int TILE = 64;   // trailing-update tile (MFMA 4 waves x 32x32)
 constexpr int UTP = 72;    // LDS pitch (doubles) of the update's operand tiles As[k][row]: the four k rows one ds_read_b64 of an MFMA operand touches start 16 banks apart (64 would put all four on the same banks)
 constexpr int S1_MAXN = 96;   // PSD blocks up to this order take the matrix-core stage 1 of ADA'
-constexpr int S1_KC = 48;     // slots (nonzero columns of A_jk) per GEMM chunk
+constexpr int S1_KC = 32;     // slots (nonzero columns of A_jk) per GEMM chunk: a multiple of 4 (the slots of one MFMA step); 2 * 32 * 80 doubles = the Z of a block of order 80
 constexpr int S1_WAVES = 8;   // wavefronts per task
 constexpr int S1_NZ = 1536;   // nonzeros of a chunk of slots staged in LDS (bigger chunks read At directly)
+// dynamic LDS of a k_psd_stage1_mfma launch (ada_psd; tests/test_stage1_mfma.py compiles these): Yl and Dl of a chunk (S1_KC slots x np), under
+// them the finished Z (n x (n | 1)), in doubles; behind them the staged nonzeros (value + row) of the plan's largest task, up to S1_NZ
+constexpr int s1_nzcap(int64_t maxnz) { return (int)(((maxnz + 1) & ~(int64_t)1) < S1_NZ ? ((maxnz + 1) & ~(int64_t)1) : S1_NZ); }
+constexpr int s1_mfma_ldsy(int maxn) { return 2 * S1_KC * ((maxn + 15) & ~15) > maxn * (maxn | 1) ? 2 * S1_KC * ((maxn + 15) & ~15) : maxn * (maxn | 1); }
+constexpr size_t s1_mfma_lds(int maxn, int64_t maxnz) { return (size_t)s1_mfma_ldsy(maxn) * sizeof(double) + (size_t)s1_nzcap(maxnz) * (sizeof(double) + sizeof(int)); }
 constexpr int S1_MAXT = ((S1_MAXN / 16) * (S1_MAXN / 16) + S1_WAVES - 1) / S1_WAVES;   // 16x16 tiles of Z per wavefront
 constexpr int S1_GEN_LDS = 74 * 1024;   // LDS target per task of the generic stage-1 kernel (bytes): two 512-work-item tasks per compute unit
 constexpr int ELL_WAVES = 8;  // wavefronts per workgroup of the ELL stage-2 kernel of ADA'
