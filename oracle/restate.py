@@ -29,8 +29,9 @@ def dsqr_vector(K, d):
 
 def getada(At, K, d, DAtq, udsqr):
     """Dense ADA' (m x m, symmetric) and absd as produced by getada1 -> getada2 -> getada3
-    (getada1.c:89-152, getada2.c:74-118, getada3.c:253-361, spscale.c:249-305, spmakesym getada3.c:151-180).
-    At is the internal N x m matrix (PSD parts folded into the lower triangle)."""
+    (getada1.c:89-152, getada2.c:74-118, getada3.c:253-361, spscale.c:249-305 and :332-435, spmakesym getada3.c:151-180).
+    At is the internal N x m matrix (PSD parts folded into the lower triangle; Hermitian blocks -- K.s entries from K.rsdpN on -- as
+    [vec(Re); vec(Im)] planes, udsqr likewise)."""
     At = sp.csc_matrix(At)
     N, m = At.shape
     s = np.asarray(K["s"], dtype=np.int64).ravel()
@@ -51,16 +52,32 @@ def getada(At, K, d, DAtq, udsqr):
     Z = np.zeros_like(Apsd)
     off = 0
     ud = np.asarray(udsqr, dtype=np.float64).ravel()
-    for n in s:                                                   # real symmetric blocks (sprealdxd)
-        D = ud[off:off + n * n].reshape(n, n, order="F")
+    nreal = int(np.asarray(K.get("rsdpN", s.size)).ravel()[0])
+    for k, n in enumerate(s):
+        if k < nreal:                                             # real symmetric blocks (sprealdxd)
+            D = ud[off:off + n * n].reshape(n, n, order="F")
+            for j in range(m):
+                x = Apsd[off:off + n * n, j]
+                if not x.any():
+                    continue
+                X = x.reshape(n, n, order="F")
+                W = D @ X @ D                                     # Z = D sym(X) D = (W + W')/2, spscale.c:283-304
+                Z[off:off + n * n, j] = ((W + W.T) / 2).ravel(order="F")
+            off += n * n
+            continue
+        # Hermitian blocks (spcpxdxd): rows [vec(Re); vec(Im)] of X and of D; Z = D herm(X) D = (W + W^H)/2 with W = D X D in
+        # complex arithmetic, its real plane read at the real rows and its imaginary plane at the imaginary rows (spscale.c:353-434)
+        D = ud[off:off + n * n].reshape(n, n, order="F") + 1j * ud[off + n * n:off + 2 * n * n].reshape(n, n, order="F")
         for j in range(m):
-            x = Apsd[off:off + n * n, j]
+            x = Apsd[off:off + 2 * n * n, j]
             if not x.any():
                 continue
-            X = x.reshape(n, n, order="F")
-            W = D @ X @ D                                         # Z = D sym(X) D = (W + W')/2, spscale.c:283-304
-            Z[off:off + n * n, j] = ((W + W.T) / 2).ravel(order="F")
-        off += n * n
+            X = x[:n * n].reshape(n, n, order="F") + 1j * x[n * n:].reshape(n, n, order="F")
+            W = D @ X @ D
+            Zc = (W + W.conj().T) / 2
+            Z[off:off + n * n, j] = Zc.real.ravel(order="F")
+            Z[off + n * n:off + 2 * n * n, j] = Zc.imag.ravel(order="F")
+        off += 2 * n * n
     ADA = ADA + Apsd.T @ Z                                        # getada3.c:333-351: ada_ij += a_i' daj
     for j in range(m):
         if Apsd[:, j].any():
