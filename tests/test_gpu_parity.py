@@ -8,6 +8,7 @@ import pytest
 import scipy.sparse as sp
 
 import helpers
+import test_pcg_ops
 from helpers import TOL, check_golden, check_iteration, ref_scaling, relerr, spd_pattern, use_hip
 
 pytestmark = pytest.mark.gpu
@@ -552,7 +553,7 @@ def test_negative_multiple_brings_a_removed_dependency_back_on_gpu(refmex, glue,
     test_negative_multiple_brings_a_removed_dependency_back(refmex, glue, seed, cfac)
 
 
-@pytest.mark.parametrize("case", range(4))
+@pytest.mark.parametrize("case", range(len(test_pcg_ops.CASES)))
 def test_pcg_operators_on_gpu(refmex, case):
     """Amul (sparse + dense columns), vecsym and psdscale (real and Hermitian blocks, with and without the
     pivot order) on the resident plan against vecsym.c and the restated Amul.m / psdscale.m."""

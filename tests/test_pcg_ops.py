@@ -45,7 +45,7 @@ def psdscale_restated(u, perm, x, K, transp):
 
 
 CASES = [dict(m=20, lp=4, q=(3,), s=(5, 7)), dict(m=30, lp=0, q=(), s=(70, 9), hs=(6,)), dict(m=12, lp=3, q=(4, 3), s=(), hs=(66, 3)),
-         dict(m=15, lp=2, q=(), s=(130,))]
+         dict(m=15, lp=2, q=(), s=(130,)), dict(m=10, lp=2, q=(), s=(3,), hs=(130,))]
 
 
 def check_pcg_ops(refmex, kw, seed=0):
@@ -81,12 +81,18 @@ def check_pcg_ops(refmex, kw, seed=0):
     if lenud:
         u, perm = scaling_factor_case(P.K, seed=seed + 3)
         plan.upload("u", u); plan.invcholfac(perm)                   # leaves the pivot order resident
-        xv = plan.download("xN", N)
-        for transp in (0, 1):
-            for use_perm in (False, True):
-                plan.psdscale(transp, use_perm)
-                want = psdscale_restated(u, perm if use_perm else None, xv, P.K, transp)
-                assert relerr(plan.download("psd", lenud), want) < TOL, (transp, use_perm)
+        ks, nr = P.K["s"].ravel().astype(int), int(P.K["rsdpN"])
+        ends = np.cumsum([n * n * (1 if k < nr else 2) for k, n in enumerate(ks)])
+        # x symmetrised by vecsym, and x as drawn: psdscale.m defines T' X T for any X (on a symmetric X a transposed fetch of X is invisible)
+        for xv in (plan.download("xN", N), rng.standard_normal(N)):
+            plan.upload("xN", xv)
+            for transp in (0, 1):
+                for use_perm in (False, True):
+                    plan.psdscale(transp, use_perm)
+                    want = psdscale_restated(u, perm if use_perm else None, xv, P.K, transp)
+                    got = plan.download("psd", lenud)
+                    for k, (g, w) in enumerate(zip(np.split(got, ends[:-1]), np.split(want, ends[:-1]))):   # per PSD block, not over the concatenation
+                        assert relerr(g, w) < TOL, (transp, use_perm, k)
     plan.close()
 
 

@@ -124,34 +124,67 @@ def whole_solve_parity(name):
 KW = dict(m=24, lp=4, q=(3, 5), s=(6, 4), hs=(3,), dens=0.4)
 
 
-def synthetic(seed=1, perm=True):
+def synthetic(seed=1, perm=True, kw=KW, P=None, graded=0.0, u_off=None, detune=("l",)):
     """a Sedumi on problem.random_sdp (LP, Lorentz, real and Hermitian PSD blocks) with a factored resident plan for a scaling
-    whose d.u comes from test_invcholfac.scaling_factor_case (lower triangle mirrored, as the scaling update stores it)"""
+    whose d.u comes from test_invcholfac.scaling_factor_case (lower triangle mirrored, as the scaling update stores it).
+    Hooks of test_wrappcg_shapes.py (the defaults leave every number of this function as it was without them):
+    kw / P: other arguments of random_sdp, or a problem built by the caller -- any cone mix, also K.l = 0, no Lorentz cone, no PSD block;
+    graded = g > 0: d.l, d.det and the diagonal of d.u are 10^(g (2 rand - 1)), spread over 2 g decades, not 0.5 + rand;
+    u_off = c: the strict upper triangle of a d.u block of order n times c / sqrt(n) (a wide random triangle is otherwise singular to rounding);
+    detune: which of "l", "det", "u" move away from the factor's scaling afterwards (the Lorentz fields and DAt.q follow d.det)"""
     from sedumi_amd import problem
     from sedumi_amd.driver import loop as lp
     from test_invcholfac import scaling_factor_case
-    P = problem.random_sdp(seed=seed, **KW)
+    if P is None:
+        P = problem.random_sdp(seed=seed, **kw)
     rng = np.random.default_rng(seed)
     N, m = P.At.shape
     S = lp.Sedumi(P.At, rng.standard_normal(m), rng.standard_normal(N), P.K, internal=True)
     cn = S.cone
-    d = S.sdinit()[0]
-    d["l"] = 0.5 + rng.random(cn.l)
-    d["det"] = 0.5 + rng.random(cn.nq)
-    d["q2"] = 0.3 * rng.standard_normal(d["q2"].size)
-    d["q1"] = np.sqrt(d["det"] + cn.ddot(d["q2"], np.concatenate((np.zeros(cn.i2), d["q2"], np.zeros(N - cn.i3)))))   # det(d.q) = d.det
-    d["auxdet"] = np.sqrt(2 * d["det"])
-    d["auxtr"] = np.sqrt(2) * (d["q1"] + d["auxdet"])
-    u, pm = scaling_factor_case(P.K, seed=seed + 3, garbage_lower=False)
+    d = {}
+
+    def spread(n):
+        return 10.0 ** (graded * (2.0 * rng.random(n) - 1.0)) if graded else 0.5 + rng.random(n)
+
+    def lorentz(det):                                                   # det(d.q) = d.det, and what updtransfo.m derives from it
+        d["det"] = det
+        d["q1"] = np.sqrt(det + cn.ddot(d["q2"], np.concatenate((np.zeros(cn.i2), d["q2"], np.zeros(N - cn.i3)))))
+        d["auxdet"] = np.sqrt(2 * det)
+        d["auxtr"] = np.sqrt(2) * (d["q1"] + d["auxdet"])
+
+    d["l"] = spread(cn.l)
+    det = spread(cn.nq)
+    d["q2"] = 0.3 * rng.standard_normal(cn.i3 - cn.i2)
+    lorentz(det)
+    if cn.lenud:
+        u, pm = scaling_factor_case(P.K, seed=seed + 3, garbage_lower=False)
+    else:
+        u, pm = np.zeros(0), np.zeros(0)
     mats = [M + np.triu(M, 1).conj().T for M, _ in cn._blocks(np.concatenate((np.zeros(cn.lq), u)))]
+    if u_off is not None or graded:
+        for k, M in enumerate(mats):
+            n = M.shape[0]
+            dg = spread(n) if graded else np.real(np.diag(M)).copy()
+            if u_off is not None:
+                M *= u_off / math.sqrt(n)
+            M[np.arange(n), np.arange(n)] = dg
     d["u"] = cn._pack(mats)
     d["perm"] = pm if perm else np.zeros(0)
     DAt = S.G.getDAtm(S.S, d)
     L = S.hot.factor(S.S, d, DAt, dict(S.S["L"]), S.pars["chol"])
     # the operator's LP scaling moved away from the factor's: the factor becomes a preconditioner that leaves the CG loop real work
     # (with the exact factor every loop would end at the rounding level of the solves, where branches are decided by the last bits)
-    d["l"] = d["l"] * (1.0 + rng.random(cn.l))
-    S.hot.plan.upload("dl", d["l"])
+    pl = S.hot.plan
+    if "l" in detune:
+        d["l"] = d["l"] * (1.0 + rng.random(cn.l))
+        pl.upload("dl", d["l"])
+    if "det" in detune and cn.nq:
+        lorentz(d["det"] * (1.0 + rng.random(cn.nq)))
+        DAt = S.G.getDAtm(S.S, d)
+        pl.upload("ddet", d["det"]); pl.upload("q1", d["q1"]); pl.getdatq()
+    if "u" in detune and cn.lenud:
+        d["u"] = cn._pack([M * (1.0 + 0.5 * rng.random()) for M, _ in cn._blocks(np.concatenate((np.zeros(cn.lq), d["u"])))])
+        pl.upload("u", d["u"])
     return S, L, d, DAt, rng
 
 
