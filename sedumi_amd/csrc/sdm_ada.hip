@@ -28,312 +28,7 @@
 
 namespace sdm {
 
-// ============================================================ host analysis
-void ada_build(sdm_plan *P, sdm_int N, sdm_int m, const sdm_int *Ajc, const sdm_int *Air, const double *Apr,
-               const sdm_int *Ajc_psd, sdm_int lpN, sdm_int lorN, const sdm_int *lorNL, sdm_int sdpN,
-               sdm_int rsdpN, const sdm_int *sdpNL, const sdm_int *qblkstart, const sdm_int *psd_blkstart,
-               const sdm_int *Qjc, const sdm_int *Qir, const sdm_int *ADAjc, const sdm_int *ADAir) {
-  AdaPlan &A = P->ada;
-  A.N = N; A.m = m; A.nnzA = Ajc[m]; A.lpN = lpN; A.lorN = lorN; A.sdpN = sdpN; A.rsdpN = rsdpN;
-  A.ic_n.release(); A.ufac.release();                                // invcholfac tables belong to the old cone
-  if (A.nnzA >= (sdm_int)1 << 31 || N >= (sdm_int)1 << 31) throw std::runtime_error("At too large for 32-bit row indices");
-  (void)lorNL;
-  A.nlq = sdpN > 0 ? psd_blkstart[0] : N;
-  if (lorN > 0 && qblkstart[lorN] != A.nlq && sdpN > 0) throw std::runtime_error("qblkstart / psd_blkstart mismatch");
-  // ---- dsqr source codes (getada1.c:106-118): -1 -> dl[r];  -2-k -> -ddet[k];  k>=0 -> ddet[k]
-  {
-    std::vector<int> code((size_t)A.nlq, -1);
-    for (sdm_int r = lpN; r < lpN + lorN && r < A.nlq; r++) code[r] = (int)(-2 - (r - lpN));
-    for (sdm_int k = 0; k < lorN; k++)
-      for (sdm_int r = qblkstart[k]; r < qblkstart[k + 1] && r < A.nlq; r++) code[r] = (int)k;
-    A.dsqr_code.upload(code);
-  }
-  // ---- PSD blocks
-  A.psd_n.assign(sdpNL, sdpNL + sdpN);
-  A.psd_start.assign(psd_blkstart, psd_blkstart + sdpN + (sdpN > 0 ? 1 : 0));
-  A.psd_udoff.assign(sdpN + 1, 0);
-  A.maxn = 0;
-  for (sdm_int k = 0; k < sdpN; k++) {
-    sdm_int n = sdpNL[k];
-    sdm_int len = (k < rsdpN ? 1 : 2) * n * n;
-    if (psd_blkstart[k + 1] - psd_blkstart[k] != len) throw std::runtime_error("PSD block size / blkstart mismatch");
-    A.psd_udoff[k + 1] = A.psd_udoff[k] + len;
-    A.maxn = std::max<int>(A.maxn, (int)n);
-  }
-  A.lenud = A.psd_udoff[sdpN];
-  // ---- per PSD nonzero: block id and position in the union pattern U_k
-  std::vector<int> Ablk((size_t)A.nnzA, -1), Aupos((size_t)A.nnzA, 0);
-  std::vector<std::vector<int>> U(sdpN);
-  for (sdm_int j = 0; j < m && sdpN > 0; j++) {
-    sdm_int k = 0;
-    for (sdm_int t = Ajc_psd[j]; t < Ajc[j + 1]; t++) {
-      sdm_int r = Air[t];
-      if (r < A.nlq) throw std::runtime_error("Ajc_psd points into the LP/Lorentz part");
-      while (k < sdpN && r >= psd_blkstart[k + 1]) k++;
-      if (k >= sdpN) throw std::runtime_error("At row index beyond the PSD blocks");
-      Ablk[t] = (int)k;
-      U[k].push_back((int)(r - psd_blkstart[k]));
-    }
-  }
-  std::vector<int64_t> uoff(sdpN + 1, 0);
-  for (sdm_int k = 0; k < sdpN; k++) {
-    std::sort(U[k].begin(), U[k].end());
-    U[k].erase(std::unique(U[k].begin(), U[k].end()), U[k].end());
-    uoff[k + 1] = uoff[k] + (int64_t)U[k].size();
-  }
-  std::vector<int> upos_all((size_t)uoff[sdpN]);
-  for (sdm_int k = 0; k < sdpN; k++) std::copy(U[k].begin(), U[k].end(), upos_all.begin() + uoff[k]);
-  sdm_int psdnnz = 0;
-  for (sdm_int j = 0; j < m && sdpN > 0; j++)
-    for (sdm_int t = Ajc_psd[j]; t < Ajc[j + 1]; t++) {
-      int k = Ablk[t];
-      int q = (int)(Air[t] - psd_blkstart[k]);
-      Aupos[t] = (int)(std::lower_bound(U[k].begin(), U[k].end(), q) - U[k].begin());
-      psdnnz++;
-    }
-  A.thread_per_row = (m > 0 && psdnnz / (double)m < 48.0);     // short rows: one pattern entry per work-item, else per wavefront
-  A.nnz_lq = A.nnzA - psdnnz;                                      // LP + Lorentz nonzeros of At
-  A.lq_maxcol = 0;
-  for (sdm_int j = 0; j < m; j++) A.lq_maxcol = std::max<int64_t>(A.lq_maxcol, (sdpN > 0 ? Ajc_psd[j] : Ajc[j + 1]) - Ajc[j]);
-  // ---- stage-1 tasks and slots
-  std::vector<int> t_col, t_blk, t_n, t_nslot, t_ulen, t_herm, s_col;
-  std::vector<int64_t> t_slotptr, t_udoff, t_uoff, t_zoff, s_nzptr, c_taskptr(m + 1, 0);
-  int64_t zlen = 0;
-  for (sdm_int j = 0; j < m; j++) {
-    sdm_int t = sdpN > 0 ? Ajc_psd[j] : Ajc[j + 1];
-    while (t < Ajc[j + 1]) {
-      int k = Ablk[t];
-      sdm_int te = t;
-      while (te < Ajc[j + 1] && Ablk[te] == k) te++;
-      const sdm_int n = A.psd_n[k];
-      const bool herm = k >= rsdpN;
-      t_col.push_back((int)j); t_blk.push_back(k); t_n.push_back((int)n); t_herm.push_back(herm ? 1 : 0);
-      t_slotptr.push_back((int64_t)s_col.size());
-      t_udoff.push_back(A.psd_udoff[k]); t_uoff.push_back(uoff[k]); t_ulen.push_back((int)U[k].size());
-      t_zoff.push_back(zlen); zlen += (int64_t)U[k].size();
-      // slots: distinct columns of X_jk (real part first, then imaginary part for Hermitian blocks)
-      int nslot = 0; sdm_int prevcol = -1; int prevpart = -1;
-      for (sdm_int u = t; u < te; u++) {
-        sdm_int q = Air[u] - psd_blkstart[k];
-        int part = q >= n * n ? 1 : 0;
-        sdm_int col = (q - part * n * n) / n;
-        if (col != prevcol || part != prevpart) {
-          s_col.push_back((int)(col + part * n)); s_nzptr.push_back((int64_t)u);
-          nslot++; prevcol = col; prevpart = part;
-        }
-      }
-      t_nslot.push_back(nslot);
-      t = te;
-    }
-    c_taskptr[j + 1] = (int64_t)t_col.size();
-  }
-  s_nzptr.push_back(A.nnzA);   // sentinel (only used through per-task end pointers)
-  { // dispatch order of the stage-1 tasks: decreasing cost (nonzeros x order + slots x order^2), so that the few heavy
-    // constraints do not form the tail of the launch
-    std::vector<int> order(t_col.size());
-    std::vector<double> cost(t_col.size());
-    for (size_t t = 0; t < t_col.size(); t++) {
-      order[t] = (int)t;
-      const double nz = (double)((t + 1 < t_slotptr.size() ? s_nzptr[t_slotptr[t + 1]] : A.nnzA) - s_nzptr[t_slotptr[t]]);
-      cost[t] = nz * t_n[t] + (double)t_nslot[t] * t_n[t] * t_n[t];
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-    A.t_order.upload(order);
-    // the generic kernel's dispatch order when there are many blocks (64 x 200): the hardware deals consecutive workgroups to the 8 XCDs
-    // in turn, and every task re-reads rows of its block's D_k through its XCD's L2 -- with the constraints in natural order every D_k
-    // was fetched by all eight L2s (246 MB of HBM traffic per launch against the 20 MB of the D_k).  So: block k's tasks go to XCD k % 8,
-    // workgroup 8 s + x takes the s-th task of XCD x's list (heaviest first inside a list); lists that run out leave their turns to the rest.
-    A.t_order_xcd.release();
-    if (sdpN >= 16 && !t_col.empty()) {
-      constexpr int NX = 8;
-      std::vector<std::vector<int>> lst(NX);
-      for (int t : order) lst[t_blk[t] % NX].push_back(t);
-      std::vector<int> ox; ox.reserve(order.size());
-      std::vector<size_t> pos(NX, 0);
-      while (ox.size() < order.size())
-        for (int x = 0; x < NX; x++) if (pos[x] < lst[x].size()) ox.push_back(lst[x][pos[x]++]);
-      A.t_order_xcd.upload(ox);
-    } }
-  A.s1_maxnz = 0;
-  for (size_t t = 0; t < t_col.size(); t++)
-    A.s1_maxnz = std::max<int64_t>(A.s1_maxnz, (t + 1 < t_slotptr.size() ? s_nzptr[t_slotptr[t + 1]] : A.nnzA) - s_nzptr[t_slotptr[t]]);
-  A.ntask = (sdm_int)t_col.size(); A.zlen = zlen;
-  A.one_task_per_col = true; A.s1_maxulen = 0;
-  for (sdm_int j = 0; j < m; j++) if (c_taskptr[j + 1] - c_taskptr[j] > 1) A.one_task_per_col = false;
-  for (size_t t = 0; t < t_ulen.size(); t++) A.s1_maxulen = std::max(A.s1_maxulen, t_ulen[t]);
-  A.h_taskptr = c_taskptr; A.col0 = 0; A.col1 = m;
-  { std::vector<int64_t> czl(m + 1, 0);                       // length of z_j (all tasks of constraint j)
-    A.zmaxj = 0;
-    for (sdm_int j = 0; j < m; j++) {
-      for (int64_t t = c_taskptr[j]; t < c_taskptr[j + 1]; t++) czl[j] += t_ulen[t];
-      A.zmaxj = std::max<int64_t>(A.zmaxj, czl[j]);
-    }
-    A.c_zlen.upload(czl); }
-  // per task: end of its last slot = start of next task's first nonzero; store explicit end pointers in s_nzptr
-  // by giving every slot an (begin) and using the next slot's begin inside a task, and the task end via t_end:
-  std::vector<int64_t> t_end(A.ntask);
-  { sdm_int ti = 0;
-    for (sdm_int j = 0; j < m; j++) {
-      sdm_int t = sdpN > 0 ? Ajc_psd[j] : Ajc[j + 1];
-      while (t < Ajc[j + 1]) { int k = Ablk[t]; sdm_int te = t; while (te < Ajc[j + 1] && Ablk[te] == k) te++; t_end[ti++] = te; t = te; }
-    } }
-  // ---- stage-2 fast path (dense-ish ADA patterns): the PSD nonzeros of At re-packed for one-row-per-lane sweeps.
-  // Rows (constraints) are sorted by their number of PSD nonzeros and cut into groups of 64; a group stores its
-  // nonzeros interleaved (entry t of all 64 rows contiguous) and padded to the longest row of the group, so that
-  // every load of the sweep is one coalesced 512-byte line and no cross-lane reduction is needed.  All wavefronts of
-  // a workgroup share every group (interleaved slices of the entry range).
-  {
-    A.ell_ok = false;
-    // z_j is staged in LDS at FULL length (all blocks, zeros where constraint j has no nonzero): an entry of the ELL
-    // copy then carries its final position uoff[k] + upos and the sweep needs one LDS gather per entry and column
-    const int64_t zmax = uoff[sdpN];
-    A.zmax = zmax;
-    const double dens = m > 0 ? (double)ADAjc[m] / ((double)m * (double)m) : 0.0;
-    const size_t lds = (size_t)zmax * sizeof(double);
-    if (sdpN > 0 && psdnnz > 0 && dens >= 0.2 && lds <= 96 * 1024 && !A.thread_per_row) {   // very short rows: one pattern entry per work-item instead
-      std::vector<int> order(m);
-      for (sdm_int j = 0; j < m; j++) order[j] = (int)j;
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return Ajc[a + 1] - Ajc_psd[a] > Ajc[b + 1] - Ajc_psd[b]; });
-      const int ng = (int)((m + 63) / 64);
-      std::vector<int> grow((size_t)ng * 64, -1), glen(ng);
-      std::vector<int64_t> goff(ng + 1, 0);
-      for (int g = 0; g < ng; g++) {
-        int len = 0;
-        for (int l = 0; l < 64 && g * 64 + l < m; l++) { const int i = order[g * 64 + l]; grow[g * 64 + l] = i; len = std::max<int>(len, (int)(Ajc[i + 1] - Ajc_psd[i])); }
-        glen[g] = len; goff[g + 1] = goff[g] + len;
-      }
-      std::vector<double> gval((size_t)goff[ng] * 64, 0.0);
-      std::vector<int> gbu((size_t)goff[ng] * 64, 0);           // position in the full-length z vector (padding: 0 with value 0)
-      for (int g = 0; g < ng; g++)
-        for (int l = 0; l < 64; l++) {
-          const int i = grow[g * 64 + l];
-          if (i < 0) continue;
-          for (sdm_int t = Ajc_psd[i]; t < Ajc[i + 1]; t++) {
-            const size_t pos = (size_t)(goff[g] + (t - Ajc_psd[i])) * 64 + l;
-            gval[pos] = Apr[t]; gbu[pos] = (int)(uoff[Ablk[t]] + Aupos[t]);
-          }
-        }
-      A.ell_ng = ng;
-      A.g_row.upload(grow); A.g_len.upload(glen); A.g_off.upload(goff); A.g_val.upload(gval); A.g_bu.upload(gbu);
-      { std::vector<int> pos((size_t)m); for (sdm_int p = 0; p < m; p++) pos[(size_t)order[p]] = (int)p; A.ell_pos.upload(pos); }
-      A.ell_order.upload(order);
-      A.ell_full = (ADAjc[m] == (sdm_int)m * m);                      // every column of the pattern full: (j, i) sits at ADAjc[i] + j
-      A.d_uoff.upload(uoff);
-      { std::vector<int> zp((size_t)A.nnzA, 0);                       // position of a PSD nonzero's entry in the full-length z vector
-        for (sdm_int i = 0; i < m; i++) for (sdm_int t = Ajc_psd[i]; t < Ajc[i + 1]; t++) zp[(size_t)t] = (int)(uoff[Ablk[t]] + Aupos[t]);
-        A.d_Azpos.upload(zp);
-        std::vector<int> zd(t_blk.size());                            // and of a task's block
-        for (size_t t = 0; t < t_blk.size(); t++) zd[t] = (int)uoff[t_blk[t]];
-        A.t_zdst.upload(zd);
-        // one record per column for the prologue of k_psd_stage2_ell, indexed by column (cdc*) and by ELL position (cdp*):
-        //   cd64[8 x + ..] = first task, first PSD nonzero, end of the column, source offset in zbuf of its first four tasks
-        //   cd32[16 x + ..] = the column, number of tasks, destination offset in z of the first four, their lengths
-        for (int byp = 0; byp < 2; byp++) {
-          std::vector<long long> c64((size_t)std::max<sdm_int>(m, 1) * 8, 0);
-          std::vector<int> c32((size_t)std::max<sdm_int>(m, 1) * 16, 0);
-          for (sdm_int x = 0; x < m; x++) {
-            const sdm_int j = byp ? order[(size_t)x] : x;
-            const int64_t tb = c_taskptr[j], te = c_taskptr[j + 1];
-            c64[8 * x] = tb; c64[8 * x + 1] = Ajc_psd[j]; c64[8 * x + 2] = Ajc[j + 1];
-            c32[16 * x] = (int)j; c32[16 * x + 1] = (int)(te - tb);
-            for (int sg = 0; sg < 4 && tb + sg < te; sg++) {
-              c64[8 * x + 3 + sg] = t_zoff[(size_t)(tb + sg)]; c32[16 * x + 2 + sg] = zd[(size_t)(tb + sg)]; c32[16 * x + 6 + sg] = t_ulen[(size_t)(tb + sg)];
-            }
-          }
-          if (byp) { A.cdp64.upload(c64); A.cdp32.upload(c32); } else { A.cdc64.upload(c64); A.cdc32.upload(c32); }
-        } }
-      A.ell_ok = true;
-    }
-  }
-  // ---- transposed-entry map of the ADA pattern
-  std::vector<int> adaT((size_t)ADAjc[m], -1);
-  { std::vector<sdm_int> nxt(ADAjc, ADAjc + m);
-    // for entry e=(i,j): find (j,i) by binary search in column i
-    for (sdm_int j = 0; j < m; j++)
-      for (sdm_int e = ADAjc[j]; e < ADAjc[j + 1]; e++) {
-        sdm_int i = ADAir[e];
-        const sdm_int *b = ADAir + ADAjc[i], *en = ADAir + ADAjc[i + 1];
-        const sdm_int *f = std::lower_bound(b, en, j);
-        if (f != en && *f == j) adaT[e] = (int)(f - ADAir);
-      } }
-  // ---- upload
-  { std::vector<int64_t> v(Ajc, Ajc + m + 1); A.d_Ajc.upload(v); }
-  { std::vector<int64_t> v(Ajc_psd, Ajc_psd + m); A.d_Ajc_psd.upload(v); }
-  { std::vector<int> v((size_t)A.nnzA); for (sdm_int t = 0; t < A.nnzA; t++) v[t] = (int)Air[t]; A.d_Air.upload(v); }
-  A.d_Apr.upload(Apr, (size_t)A.nnzA);
-  A.d_Ablk.upload(Ablk); A.d_Aupos.upload(Aupos);
-  A.nnzQ = lorN > 0 ? Qjc[m] : 0;
-  A.q_maxcol = 0;
-  for (sdm_int j = 0; j < m && lorN > 0; j++) A.q_maxcol = std::max<int64_t>(A.q_maxcol, Qjc[j + 1] - Qjc[j]);
-  { std::vector<int64_t> v(m + 1, 0); if (lorN > 0) v.assign(Qjc, Qjc + m + 1); A.d_Qjc.upload(v); }
-  { std::vector<int> v((size_t)A.nnzQ); for (sdm_int t = 0; t < A.nnzQ; t++) v[t] = (int)Qir[t]; A.d_Qir.upload(v); }
-  { std::vector<int64_t> v(ADAjc, ADAjc + m + 1); A.d_ADAjc.upload(v); }
-  { std::vector<int> v((size_t)ADAjc[m]); for (sdm_int t = 0; t < ADAjc[m]; t++) v[t] = (int)ADAir[t]; A.d_ADAir.upload(v); }
-  A.d_ADAT.upload(adaT);
-  A.u_pos.upload(upos_all);
-  { std::vector<int> urc(upos_all.size(), 0);                        // (r << 16) | c of a real block's target (k_psd_stage1_mfma: no division per target)
-    for (sdm_int k = 0; k < std::min(sdpN, rsdpN); k++) {
-      const int n = (int)A.psd_n[k];
-      if (n >= 65536) continue;
-      for (size_t u = 0; u < U[k].size(); u++) { const int q = U[k][u], c = q / n, r = q - c * n; urc[(size_t)uoff[k] + u] = (r << 16) | c; }
-    }
-    A.u_rc.upload(urc); }
-  A.t_col.upload(t_col); A.t_blk.upload(t_blk); A.t_n.upload(t_n); A.t_nslot.upload(t_nslot); A.t_ulen.upload(t_ulen);
-  A.t_herm.upload(t_herm);
-  A.t_slotptr.upload(t_slotptr); A.t_udoff.upload(t_udoff); A.t_uoff.upload(t_uoff); A.t_zoff.upload(t_zoff);
-  A.s_col.upload(s_col); A.s_nzptr.upload(s_nzptr); A.c_taskptr.upload(c_taskptr);
-  A.t_end.upload(t_end);
-  { std::vector<int64_t> v(A.psd_start.begin(), A.psd_start.end()); if (v.empty()) v.push_back(0); A.d_psd_start.upload(v); }
-  A.zbuf.alloc((size_t)std::max<int64_t>(zlen, 1));
-  A.dsqr.alloc((size_t)std::max<sdm_int>(A.nlq, 1));
-  A.dl.alloc((size_t)std::max<sdm_int>(lpN, 1)); A.ddet.alloc((size_t)std::max<sdm_int>(lorN, 1));
-  A.qpr.alloc((size_t)std::max<sdm_int>(A.nnzQ, 1)); A.udsqr.alloc((size_t)std::max<sdm_int>(A.lenud, 1));
-  { std::vector<int64_t> v(lorN + 1, A.nlq); for (sdm_int k = 0; k <= lorN && lorN > 0; k++) v[k] = qblkstart[k]; A.d_qblk.upload(v); }
-  A.q1.alloc((size_t)std::max<sdm_int>(lorN, 1));
-  A.q2.alloc((size_t)std::max<sdm_int>(lorN > 0 ? qblkstart[lorN] - qblkstart[0] : 0, 1));
-  A.symtmp.alloc((size_t)std::max<sdm_int>(ADAjc[m], 1));
-  // ---- dense-column form of the LP / Lorentz part.  A sparse-sparse dot per ADA' entry (k_ada_spdot) is the right
-  // tool for sparse columns; when the columns are dense-ish (nb.mat: 66 %) the same sums are a weighted Gram matrix
-  // A' diag(dsqr) A, i.e. GEMM-shaped work for the matrix cores.  Static data (At) is expanded once here.
-  {
-    sdm_int nz = 0;
-    for (sdm_int j = 0; j < m; j++) nz += Ajc_psd[j] - Ajc[j];
-    const double cells = (double)A.nlq * (double)m;
-    A.lq_dense = A.nlq > 0 && m > 1 && nz > 0 && (double)nz >= 0.10 * cells && cells * 8.0 <= 1.0e9;
-    A.q_dense = lorN > 0 && A.nnzQ > 0 && (double)A.nnzQ >= 0.10 * (double)lorN * (double)m && (double)lorN * m * 8.0 <= 1.0e9;
-    if (A.lq_dense) {
-      std::vector<double> D((size_t)A.nlq * (size_t)m, 0.0);
-      for (sdm_int j = 0; j < m; j++)
-        for (sdm_int t = Ajc[j]; t < Ajc_psd[j]; t++) D[(size_t)j * (size_t)A.nlq + (size_t)Air[t]] = Apr[t];
-      A.Alq_d.upload(D);
-    } else A.Alq_d.release();
-    if (A.q_dense) {
-      std::vector<int64_t> dst((size_t)A.nnzQ);
-      for (sdm_int j = 0; j < m; j++)
-        for (sdm_int t = Qjc[j]; t < Qjc[j + 1]; t++) dst[(size_t)t] = (int64_t)j * lorN + Qir[t];
-      A.q_dst.upload(dst);
-      A.Q_d.alloc((size_t)lorN * (size_t)m);
-      if (A.lq_dense && (double)lorN * (double)m <= 1.6e7) {          // inverse map for the fused form (ada_lq_q)
-        std::vector<int> src((size_t)lorN * (size_t)m, -1);
-        for (sdm_int t = 0; t < A.nnzQ; t++) src[(size_t)dst[(size_t)t]] = (int)t;
-        A.q_src.upload(src);
-      } else A.q_src.release();
-    } else { A.Q_d.release(); A.q_dst.release(); A.q_src.release(); }
-    if (A.lq_dense || A.q_dense) {
-      const int nt = (int)((m + TILE - 1) / TILE), T = nt * (nt + 1) / 2;
-      const sdm_int rows = std::max(A.lq_dense ? A.nlq : 0, A.q_dense ? lorN : 0);
-      A.gram_split = (int)std::max<sdm_int>(1, std::min<sdm_int>((rows + TILE - 1) / TILE, std::max(1, 512 / T)));
-      A.gram_part.alloc((size_t)A.gram_split * (size_t)m * (size_t)m);
-    } else A.gram_part.release();
-  }
-  // LDS budget for stage 1: Y chunk of CC slots x n rows
-  A.stage1_lds = 96 * 1024;
-  { const size_t need = (size_t)(sdpN > rsdpN ? 4 : 2) * (size_t)A.maxn * sizeof(double);     // one slot: Y (+Yi) and D(col,:) (+Im)
-    if (need > A.stage1_lds) A.stage1_lds = need; }
-  if (A.stage1_lds > 136 * 1024) throw std::runtime_error("PSD block too large for the LDS-staged D*A*D kernel (n > 8700)");
-  P->has_ada = true;
-}
-
+// (the tables the kernels read: ada_build, sdm_ada_build.hip)
 // ================================================================= kernels
 __global__ void k_dsqr(double *dsqr, const int *code, const double *dl, const double *ddet, int nlq) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1329,6 +1024,27 @@ void ada_zero_flush(sdm_plan *P) {
   if (A.zero_ptr && A.zero_n > 0) SDM_HIP_CHECK(hipMemsetAsync(A.zero_ptr, 0, (size_t)A.zero_n * sizeof(double), P->stream));
   A.zero_ptr = nullptr; A.zero_n = 0;
 }
+// val(i,j) = sum_r M(r,i) w(r) M(r,j) on the pattern of the panel, M given by its column ranges, row indices and values (k_ada_spdot)
+static void launch_spdot(sdm_plan *P, double *ada, const int64_t *Mbeg, const int64_t *Mend, const int *Mir, const double *Mpr, const double *wgt,
+                         int64_t maxcol, const int *d_invperm, bool accumulate) {
+  AdaPlan &A = P->ada;
+  if (maxcol <= 256)                                                 // (measured: 200 nonzeros per column are still faster four entries at a time;
+                                                                     //  ONE column of 793 is not: its single entry is the whole launch)
+    SDM_KLAUNCH(P, k_ada_spdot<16>, dim3((unsigned)(A.col1 - A.col0)), dim3(256), (size_t)SPDOT_CAP * 12, ada, A.d_ADAjc.p, A.d_ADAir.p, Mbeg, Mend,
+               Mir, Mpr, wgt, d_invperm, accumulate ? 1 : 0, (int)A.col0, SPDOT_CAP);
+  else
+    SDM_KLAUNCH(P, k_ada_spdot<64>, dim3((unsigned)(A.col1 - A.col0)), dim3(256), (size_t)SPDOT_CAP * 12, ada, A.d_ADAjc.p, A.d_ADAir.p, Mbeg, Mend,
+               Mir, Mpr, wgt, d_invperm, accumulate ? 1 : 0, (int)A.col0, SPDOT_CAP);
+}
+// G = M' diag(w) M (+ M2' M2) of dense column-major operands on the matrix cores, then its entries into the pattern of the panel
+static void launch_gram(sdm_plan *P, double *ada, const double *M, const double *wgt, sdm_int R, const double *M2, sdm_int R2, const int *d_invperm,
+                        bool accumulate, double *absd) {
+  AdaPlan &A = P->ada;
+  const int m = (int)A.m, nt = (m + TILE - 1) / TILE;
+  SDM_KLAUNCH(P, k_gram_tile, dim3(nt * (nt + 1) / 2, A.gram_split), dim3(256), 0, M, wgt, (int)R, m, A.gram_split, A.gram_part.p, M2, (int)R2);
+  SDM_KLAUNCH(P, k_gram_scatter, dim3((unsigned)(A.col1 - A.col0)), dim3(128), 0, ada, A.d_ADAjc.p, A.d_ADAir.p, A.gram_part.p,
+              A.gram_split, m, d_invperm, accumulate ? 1 : 0, (int)A.col0, absd);
+}
 void ada_lq(sdm_plan *P, double *ada, const int *d_invperm, bool accumulate) {
   AdaPlan &A = P->ada;
   if (A.col1 <= A.col0) return;
@@ -1343,21 +1059,8 @@ void ada_lq(sdm_plan *P, double *ada, const int *d_invperm, bool accumulate) {
   }
   if (A.nlq > 0)
     SDM_KLAUNCH(P, k_dsqr, dim3((unsigned)((A.nlq + 255) / 256)), dim3(256), 0, A.dsqr.p, A.dsqr_code.p, A.dl.p, A.ddet.p, (int)A.nlq);
-  if (A.lq_dense) {
-    const int m = (int)A.m, nt = (m + TILE - 1) / TILE;
-    SDM_KLAUNCH(P, k_gram_tile, dim3(nt * (nt + 1) / 2, A.gram_split), dim3(256), 0, A.Alq_d.p, A.dsqr.p, (int)A.nlq, m, A.gram_split,
-                A.gram_part.p);
-    SDM_KLAUNCH(P, k_gram_scatter, dim3((unsigned)(A.col1 - A.col0)), dim3(128), 0, ada, A.d_ADAjc.p, A.d_ADAir.p, A.gram_part.p,
-                A.gram_split, m, d_invperm, accumulate ? 1 : 0, (int)A.col0);
-    return;
-  }
-  if (A.lq_maxcol <= 256)                                            // (measured: 200 nonzeros per column are still faster four entries at a time;
-                                                                     //  ONE column of 793 is not: its single entry is the whole launch)
-    SDM_KLAUNCH(P, k_ada_spdot<16>, dim3((unsigned)(A.col1 - A.col0)), dim3(256), (size_t)SPDOT_CAP * 12, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_Ajc.p, A.d_Ajc_psd.p,
-               A.d_Air.p, A.d_Apr.p, A.dsqr.p, d_invperm, accumulate ? 1 : 0, (int)A.col0, SPDOT_CAP);
-  else
-    SDM_KLAUNCH(P, k_ada_spdot<64>, dim3((unsigned)(A.col1 - A.col0)), dim3(256), (size_t)SPDOT_CAP * 12, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_Ajc.p, A.d_Ajc_psd.p,
-               A.d_Air.p, A.d_Apr.p, A.dsqr.p, d_invperm, accumulate ? 1 : 0, (int)A.col0, SPDOT_CAP);
+  if (A.lq_dense) launch_gram(P, ada, A.Alq_d.p, A.dsqr.p, A.nlq, nullptr, 0, d_invperm, accumulate, nullptr);
+  else launch_spdot(P, ada, A.d_Ajc.p, A.d_Ajc_psd.p, A.d_Air.p, A.d_Apr.p, A.dsqr.p, A.lq_maxcol, d_invperm, accumulate);
 }
 void ada_datq(sdm_plan *P) {
   AdaPlan &A = P->ada;
@@ -1370,49 +1073,69 @@ void ada_q(sdm_plan *P, double *ada, const int *d_invperm, bool accumulate) {
   if (A.lorN == 0 || A.nnzQ == 0 || A.col1 <= A.col0) return;
   ada_zero_flush(P);
   if (A.q_dense) {
-    const int m = (int)A.m, nt = (m + TILE - 1) / TILE;
-    SDM_HIP_CHECK(hipMemsetAsync(A.Q_d.p, 0, (size_t)A.lorN * (size_t)m * sizeof(double), P->stream));
+    SDM_HIP_CHECK(hipMemsetAsync(A.Q_d.p, 0, (size_t)A.lorN * (size_t)A.m * sizeof(double), P->stream));
     SDM_KLAUNCH(P, k_q_densify, dim3((unsigned)((A.nnzQ + 255) / 256)), dim3(256), 0, A.Q_d.p, A.qpr.p, A.q_dst.p, (int64_t)A.nnzQ);
-    SDM_KLAUNCH(P, k_gram_tile, dim3(nt * (nt + 1) / 2, A.gram_split), dim3(256), 0, A.Q_d.p, (const double *)nullptr, (int)A.lorN, m,
-                A.gram_split, A.gram_part.p);
-    SDM_KLAUNCH(P, k_gram_scatter, dim3((unsigned)(A.col1 - A.col0)), dim3(128), 0, ada, A.d_ADAjc.p, A.d_ADAir.p, A.gram_part.p,
-                A.gram_split, m, d_invperm, accumulate ? 1 : 0, (int)A.col0);
-    return;
-  }
-  if (A.q_maxcol <= 256)
-    SDM_KLAUNCH(P, k_ada_spdot<16>, dim3((unsigned)(A.col1 - A.col0)), dim3(256), (size_t)SPDOT_CAP * 12, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_Qjc.p, A.d_Qjc.p + 1,
-               A.d_Qir.p, A.qpr.p, (const double *)nullptr, d_invperm, accumulate ? 1 : 0, (int)A.col0, SPDOT_CAP);
-  else
-    SDM_KLAUNCH(P, k_ada_spdot<64>, dim3((unsigned)(A.col1 - A.col0)), dim3(256), (size_t)SPDOT_CAP * 12, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_Qjc.p, A.d_Qjc.p + 1,
-               A.d_Qir.p, A.qpr.p, (const double *)nullptr, d_invperm, accumulate ? 1 : 0, (int)A.col0, SPDOT_CAP);
+    launch_gram(P, ada, A.Q_d.p, nullptr, A.lorN, nullptr, 0, d_invperm, accumulate, nullptr);
+  } else launch_spdot(P, ada, A.d_Qjc.p, A.d_Qjc.p + 1, A.d_Qir.p, A.qpr.p, nullptr, A.q_maxcol, d_invperm, accumulate);
 }
 // LP + Lorentz-det part and Lorentz rank-1 part of a FULL ADA' in three launches when both take the dense Gram form
 // (nb.mat's shape): prep (dsqr, dense DAt.q), one Gram launch over the rows of both operands, one scatter -- instead of
 // eight operations.  Returns false when the case does not apply (the caller then runs ada_lq + ada_q).
 bool ada_lq_q(sdm_plan *P, double *ada) {
   AdaPlan &A = P->ada;
-  const int m = (int)A.m;
   if (!(A.lq_dense && A.q_dense && A.q_src.n && A.col0 == 0 && A.col1 == A.m && A.lorN > 0 && A.nnzQ > 0)) return false;
-  const int64_t nq = (int64_t)A.lorN * m, nprep = std::max<int64_t>(nq, A.nlq);
-  const int nt = (m + TILE - 1) / TILE;
+  const int64_t nq = (int64_t)A.lorN * (int)A.m, nprep = std::max<int64_t>(nq, A.nlq);
   SDM_KLAUNCH(P, k_lq_q_prep, dim3((unsigned)((nprep + 255) / 256)), dim3(256), 0, A.dsqr.p, A.dsqr_code.p, A.dl.p, A.ddet.p, (int)A.nlq,
               A.Q_d.p, A.qpr.p, A.q_src.p, nq);
-  SDM_KLAUNCH(P, k_gram_tile, dim3(nt * (nt + 1) / 2, A.gram_split), dim3(256), 0, A.Alq_d.p, A.dsqr.p, (int)A.nlq, m, A.gram_split,
-              A.gram_part.p, A.Q_d.p, (int)A.lorN);
-  SDM_KLAUNCH(P, k_gram_scatter, dim3((unsigned)m), dim3(128), 0, ada, A.d_ADAjc.p, A.d_ADAir.p, A.gram_part.p, A.gram_split, m,
-              (const int *)nullptr, 0, 0, A.sdpN == 0 ? P->absd.p : (double *)nullptr);
+  launch_gram(P, ada, A.Alq_d.p, A.dsqr.p, A.nlq, A.Q_d.p, A.lorN, nullptr, false, A.sdpN == 0 ? P->absd.p : nullptr);
   return true;
 }
+// spmakesym of ADA' in place, by way of A.symtmp
+static void symmetrize_in_place(sdm_plan *P, double *ada) {
+  AdaPlan &A = P->ada;
+  SDM_KLAUNCH(P, k_symmetrize, dim3((int)A.m), dim3(128), 0, A.symtmp.p, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_ADAT.p, (int)A.m);
+  SDM_HIP_CHECK(hipMemcpyAsync(ada, A.symtmp.p, A.symtmp.n * sizeof(double), hipMemcpyDeviceToDevice, P->stream));
+}
+static Stage1Tab stage1_tab(const AdaPlan &A) {
+  Stage1Tab T;
+  T.t_n = A.t_n.p; T.t_nslot = A.t_nslot.p; T.t_ulen = A.t_ulen.p; T.t_herm = A.t_herm.p; T.s_col = A.s_col.p;
+  T.u_pos = A.u_pos.p; T.u_rc = A.u_rc.p; T.Air = A.d_Air.p; T.t_slotptr = A.t_slotptr.p; T.t_udoff = A.t_udoff.p; T.t_uoff = A.t_uoff.p;
+  T.t_zoff = A.t_zoff.p; T.t_end = A.t_end.p; T.s_nzptr = A.s_nzptr.p; T.Apr = A.d_Apr.p; T.t_blk = A.t_blk.p;
+  T.psd_start = A.d_psd_start.p;
+  return T;
+}
+static Stage2Ride stage2_ride(sdm_plan *P, double *ada, const int *d_invperm) {
+  const AdaPlan &A = P->ada;
+  Stage2Ride R2 = {};
+  R2.ada = ada; R2.absd = P->absd.p; R2.ADAjc = A.d_ADAjc.p; R2.Ajc = A.d_Ajc.p; R2.Ajc_psd = A.d_Ajc_psd.p; R2.ADAir = A.d_ADAir.p;
+  R2.Ablk = A.d_Ablk.p; R2.Aupos = A.d_Aupos.p; R2.t_col = A.t_col.p; R2.invperm = d_invperm; R2.Apr = A.d_Apr.p;
+  return R2;
+}
+// the ELL sweep of stage 2 with JB columns per workgroup.  sym: the symmetric half-sweep (rows in ELL order, records by ELL position);
+// cleared: stage 1 has written the zeros of the panel's LP / Lorentz part, so the sweep stores instead of adding
+template <int JB>
+static void launch_stage2_ell(sdm_plan *P, double *ada, const int *d_invperm, int ncols, int jbase, bool sym, int gsplit, bool cleared) {
+  AdaPlan &A = P->ada;
+  const size_t lds = (size_t)JB * (size_t)A.zmax * sizeof(double);
+#ifndef SDM_EMU
+  if (lds > 48 * 1024) SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_psd_stage2_ell<JB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+#endif
+  SDM_KLAUNCH_AS(P, P->stream, JB == 4 ? "k_psd_stage2_ell<4>" : JB == 2 ? "k_psd_stage2_ell<2>" : "k_psd_stage2_ell<1>", k_psd_stage2_ell<JB>,
+                 dim3((ncols + JB - 1) / JB, gsplit), dim3(64 * ELL_WAVES), lds, ada, P->absd.p, A.d_ADAjc.p, A.d_ADAir.p,
+                 A.d_Ajc.p, A.d_Ajc_psd.p, A.d_Apr.p, A.d_Ablk.p, A.d_Aupos.p, A.c_taskptr.p, A.t_blk.p, A.t_ulen.p,
+                 A.t_zoff.p, A.zbuf.p, A.d_uoff.p, A.g_row.p, A.g_len.p, A.g_off.p, A.g_val.p, A.g_bu.p, A.ell_ng, d_invperm,
+                 (int)A.zmax, (int)A.m, jbase, jbase + ncols, A.ell_pos.p, sym ? (const int *)A.ell_order.p : (const int *)nullptr,
+                 A.d_Azpos.p, A.t_zdst.p, cleared ? 1 : 0,
+                 sym ? (const long long *)A.cdp64.p : (const long long *)A.cdc64.p, sym ? (const int *)A.cdp32.p : (const int *)A.cdc32.p);
+}
+// The PSD part of the panel, added to what ada holds (sym_input: after symmetrising that).  One of: the pairwise form (k_psd_direct*),
+// or stage 1 (matrix cores / generic, the generic one with stage 2 riding where it can) followed by stage 2 (ELL sweep / plain)
 void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, bool absd_done) {
   AdaPlan &A = P->ada;
-  hipStream_t st = P->stream;
   const int m = (int)A.m;
   if (A.sdpN == 0 || sym_input || A.col1 <= A.col0) ada_zero_flush(P);
   if (A.sdpN == 0) {
-    if (sym_input) {
-      SDM_KLAUNCH(P, k_symmetrize, dim3(m), dim3(128), 0, A.symtmp.p, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_ADAT.p, m);
-      SDM_HIP_CHECK(hipMemcpyAsync(ada, A.symtmp.p, A.symtmp.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
+    if (sym_input) symmetrize_in_place(P, ada);
     if (!absd_done) SDM_KLAUNCH(P, k_diag, dim3((m + 255) / 256), dim3(256), 0, P->absd.p, ada, A.d_ADAjc.p, A.d_ADAir.p, m);
     return;
   }
@@ -1429,14 +1152,11 @@ void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, boo
   const bool direct_zero = direct && !sym_input && !d_invperm && A.zero_ptr == ada + P->ada_jc[A.col0] &&
                            A.zero_n == (long long)(P->ada_jc[A.col1] - P->ada_jc[A.col0]);
   if (direct_zero) { A.zero_ptr = nullptr; A.zero_n = 0; }
-  if (direct || ntask <= 0 || !(A.maxn <= S1_MAXN && A.sdpN == A.rsdpN)) ada_zero_flush(P);
+  const bool s1_mfma = A.maxn <= S1_MAXN && A.sdpN == A.rsdpN;        // every block real and small enough for the matrix-core stage 1
+  if (direct || ntask <= 0 || !s1_mfma) ada_zero_flush(P);
   if (direct) {
-    if (sym_input) {
-      SDM_KLAUNCH(P, k_symmetrize, dim3(m), dim3(128), 0, A.symtmp.p, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_ADAT.p, m);
-      SDM_HIP_CHECK(hipMemcpyAsync(ada, A.symtmp.p, A.symtmp.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
+    if (sym_input) symmetrize_in_place(P, ada);
     const int nb = (int)A.sdpN;
-    const size_t lds = direct_lds;
     // full columns (a dense ADA' pattern) and no skipped triangle: DIRECT_JB columns per workgroup, constraint i looked up once per row
     const size_t lds_cols = (size_t)DIRECT_JB * (direct_lds + 16) + (size_t)A.sdpN * sizeof(int);
     if (!d_invperm && (int64_t)(P->ada_jc[A.col1] - P->ada_jc[A.col0]) == (int64_t)ncols * m && lds_cols <= S1_DIRECT_LDS_MAX) {
@@ -1444,27 +1164,21 @@ void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, boo
       SDM_KLAUNCH(P, k_psd_direct_cols, dim3((ncols + DIRECT_JB - 1) / DIRECT_JB, ysplit), dim3(256), lds_cols, ada, P->absd.p, A.d_ADAjc.p, A.d_Ajc.p, A.d_Ajc_psd.p, A.d_Apr.p,
                   A.d_Air.p, A.d_Ablk.p, A.c_taskptr.p, A.t_blk.p, A.t_n.p, A.t_udoff.p, A.t_slotptr.p, A.s_nzptr.p, A.t_end.p, A.d_psd_start.p, A.udsqr.p,
                   nb, jbase, jbase + ncols, m, direct_zero ? 1 : 0);
-      SDM_HIP_CHECK(hipGetLastError());
-      return;
-    }
-    SDM_KLAUNCH(P, k_psd_direct, dim3(ncols), dim3(256), lds, ada, P->absd.p, A.d_ADAjc.p, A.d_ADAir.p, A.d_Ajc.p, A.d_Ajc_psd.p, A.d_Apr.p, A.d_Air.p,
-                A.d_Ablk.p, A.c_taskptr.p, A.t_blk.p, A.t_n.p, A.t_udoff.p, A.t_slotptr.p, A.s_nzptr.p, A.t_end.p, A.d_psd_start.p, A.udsqr.p,
-                d_invperm, nb, jbase, direct_zero ? 1 : 0);
+    } else
+      SDM_KLAUNCH(P, k_psd_direct, dim3(ncols), dim3(256), direct_lds, ada, P->absd.p, A.d_ADAjc.p, A.d_ADAir.p, A.d_Ajc.p, A.d_Ajc_psd.p, A.d_Apr.p, A.d_Air.p,
+                  A.d_Ablk.p, A.c_taskptr.p, A.t_blk.p, A.t_n.p, A.t_udoff.p, A.t_slotptr.p, A.s_nzptr.p, A.t_end.p, A.d_psd_start.p, A.udsqr.p,
+                  d_invperm, nb, jbase, direct_zero ? 1 : 0);
     SDM_HIP_CHECK(hipGetLastError());
     return;
   }
   bool stage1_cleared_all = false;                                   // the LP / Lorentz part of the panel is zero and stage 1 has written those zeros
   if (ntask > 0) {
-    Stage1Tab T;
-    T.t_n = A.t_n.p; T.t_nslot = A.t_nslot.p; T.t_ulen = A.t_ulen.p; T.t_herm = A.t_herm.p; T.s_col = A.s_col.p;
-    T.u_pos = A.u_pos.p; T.u_rc = A.u_rc.p; T.Air = A.d_Air.p; T.t_slotptr = A.t_slotptr.p; T.t_udoff = A.t_udoff.p; T.t_uoff = A.t_uoff.p;
-    T.t_zoff = A.t_zoff.p; T.t_end = A.t_end.p; T.s_nzptr = A.s_nzptr.p; T.Apr = A.d_Apr.p; T.t_blk = A.t_blk.p;
-    T.psd_start = A.d_psd_start.p;
+    const Stage1Tab T = stage1_tab(A);
 #ifndef SDM_EMU
     SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_psd_stage1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)A.stage1_lds));
 #endif
     const int nzcap = s1_nzcap(A.s1_maxnz);
-    if (A.maxn <= S1_MAXN && A.sdpN == A.rsdpN) {
+    if (s1_mfma) {
       // LDS per task: Yl and Dl of a chunk (S1_KC slots x np), under them the finished Z (n x (n | 1)); behind them the nonzeros of the
       // plan's largest task.  At maxn = 70 that is 40 960 + 7 584 bytes (+ the kernel's static slot table): three tasks per compute unit
       const int ldsy = s1_mfma_ldsy(A.maxn);
@@ -1477,8 +1191,7 @@ void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, boo
       stage1_cleared_all = zp == ada + P->ada_jc[A.col0] && zn == (long long)(P->ada_jc[A.col1] - P->ada_jc[A.col0]);
       SDM_KLAUNCH(P, k_psd_stage1_mfma, dim3((unsigned)ntask), dim3(64 * S1_WAVES), lds, T, A.udsqr.p, A.zbuf.p, ldsy, nzcap, task0,
                   (ntask == (int)A.ntask) ? (const int *)A.t_order.p : (const int *)nullptr, zp, zn);
-    } else
-    {
+    } else {
       // LDS per task: at least one slot (Y and D row, x2 for Hermitian); beyond that S1_GEN_LDS -- several tasks per CU
       // hide each other's latencies better than one task with all its slots resident
       const size_t one = (size_t)(A.sdpN > A.rsdpN ? 4 : 2) * (size_t)A.maxn * sizeof(double);
@@ -1490,45 +1203,20 @@ void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, boo
       // every constraint touches at most one PSD block and the pattern is swept one entry per work-item: stage 2 rides in the task
       const bool ride = A.one_task_per_col && A.thread_per_row && !A.ell_ok && A.sdpN == A.rsdpN && A.s1_maxulen <= 6 * 512 &&
                         (int64_t)A.s1_maxulen * (int64_t)sizeof(double) <= (int64_t)ldsy;
-      Stage2Ride R2 = {};
       if (ride) {
-        if (sym_input) {
-          SDM_KLAUNCH(P, k_symmetrize, dim3(m), dim3(128), 0, A.symtmp.p, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_ADAT.p, m);
-          SDM_HIP_CHECK(hipMemcpyAsync(ada, A.symtmp.p, A.symtmp.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        SDM_HIP_CHECK(hipMemsetAsync(P->absd.p + jbase, 0, (size_t)ncols * sizeof(double), st));      // (constraints without PSD nonzeros: absd = 0)
-        R2.ada = ada; R2.absd = P->absd.p; R2.ADAjc = A.d_ADAjc.p; R2.Ajc = A.d_Ajc.p; R2.Ajc_psd = A.d_Ajc_psd.p; R2.ADAir = A.d_ADAir.p;
-        R2.Ablk = A.d_Ablk.p; R2.Aupos = A.d_Aupos.p; R2.t_col = A.t_col.p; R2.invperm = d_invperm; R2.Apr = A.d_Apr.p;
+        if (sym_input) symmetrize_in_place(P, ada);
+        SDM_HIP_CHECK(hipMemsetAsync(P->absd.p + jbase, 0, (size_t)ncols * sizeof(double), P->stream));      // (constraints without PSD nonzeros: absd = 0)
       }
-      SDM_KLAUNCH(P, k_psd_stage1, dim3((unsigned)ntask), dim3(512), lds, T, A.udsqr.p, A.zbuf.p, (int)(ldsy / sizeof(double)), task0, nzcap, R2,
+      SDM_KLAUNCH(P, k_psd_stage1, dim3((unsigned)ntask), dim3(512), lds, T, A.udsqr.p, A.zbuf.p, (int)(ldsy / sizeof(double)), task0, nzcap,
+                  ride ? stage2_ride(P, ada, d_invperm) : Stage2Ride{},
                   (ntask == (int)A.ntask && A.t_order_xcd.n == (size_t)ntask) ? (const int *)A.t_order_xcd.p : (const int *)nullptr);
       if (ride) { SDM_HIP_CHECK(hipGetLastError()); return; }
     }
   }
   // the reference first adds the PSD part on one triangle and symmetrises at the very end; summing the
   // transposed partial sums of getada1/2 first and adding the (symmetric) PSD part afterwards is the same sum.
-  if (sym_input) {
-    SDM_KLAUNCH(P, k_symmetrize, dim3(m), dim3(128), 0, A.symtmp.p, ada, A.d_ADAjc.p, A.d_ADAir.p, A.d_ADAT.p, m);
-    SDM_HIP_CHECK(hipMemcpyAsync(ada, A.symtmp.p, A.symtmp.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
+  if (sym_input) symmetrize_in_place(P, ada);
   if (A.ell_ok) {
-    auto lds_of = [&](int jb) { return (size_t)jb * (size_t)A.zmax * sizeof(double); };
-#define SDM_STAGE2_ELL(JB)                                                                                              \
-    do {                                                                                                                 \
-      const size_t lds = lds_of(JB);                                                                                    \
-      SDM_STAGE2_ATTR(JB, lds);                                                                                         \
-      SDM_KLAUNCH(P, k_psd_stage2_ell<JB>, dim3((ncols + JB - 1) / JB, gsplit), dim3(64 * ELL_WAVES), lds, ada, P->absd.p, A.d_ADAjc.p, A.d_ADAir.p, \
-                  A.d_Ajc.p, A.d_Ajc_psd.p, A.d_Apr.p, A.d_Ablk.p, A.d_Aupos.p, A.c_taskptr.p, A.t_blk.p, A.t_ulen.p,    \
-                  A.t_zoff.p, A.zbuf.p, A.d_uoff.p, A.g_row.p, A.g_len.p, A.g_off.p, A.g_val.p, A.g_bu.p, A.ell_ng, d_invperm, \
-                  (int)A.zmax, m, jbase, jbase + ncols, A.ell_pos.p, sym ? (const int *)A.ell_order.p : (const int *)nullptr,     \
-                  A.d_Azpos.p, A.t_zdst.p, stage1_cleared_all && !sym_input ? 1 : 0,                                             \
-                  sym ? (const long long *)A.cdp64.p : (const long long *)A.cdc64.p, sym ? (const int *)A.cdp32.p : (const int *)A.cdc32.p); \
-    } while (0)
-#ifndef SDM_EMU
-#define SDM_STAGE2_ATTR(JB, lds) if ((lds) > 48 * 1024) SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_psd_stage2_ell<JB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)))
-#else
-#define SDM_STAGE2_ATTR(JB, lds) (void)(lds)
-#endif
     // as many columns per workgroup as fit 96 KB of LDS (each coalesced load of the ELL copy then feeds JB columns)
     // The row groups of a column set (distinct rows = distinct output entries, nothing to combine) can be dealt to
     // several workgroups (gridDim.y).  Measured on the bench workload with 3: 65 -> 62 us, but 2.3x the HBM traffic
@@ -1537,15 +1225,12 @@ void ada_psd(sdm_plan *P, double *ada, const int *d_invperm, bool sym_input, boo
     // symmetric half-sweep: the whole of a full-pattern ADA' is being formed and nothing restricts the entries touched
     const bool sym = A.ell_full && !d_invperm && jbase == 0 && ncols == m;
     const int gsplit = sym ? 3 : 1;                                     // half-sweep: the long sweeps (early groups) split in three (measured 1: 52.7, 2: 41.6, 3: 38.9, 4: 41.2 us)
-    if (lds_of(4) <= 64 * 1024 && m >= 1024) SDM_STAGE2_ELL(4);
-    else if (lds_of(2) <= 64 * 1024 && m >= 512) SDM_STAGE2_ELL(2);
-    else SDM_STAGE2_ELL(1);
-#undef SDM_STAGE2_ELL
-#undef SDM_STAGE2_ATTR
-    SDM_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  {
+    const bool cleared = stage1_cleared_all && !sym_input;
+    const size_t zbytes = (size_t)A.zmax * sizeof(double);              // LDS per column of a workgroup
+    if (4 * zbytes <= 64 * 1024 && m >= 1024) launch_stage2_ell<4>(P, ada, d_invperm, ncols, jbase, sym, gsplit, cleared);
+    else if (2 * zbytes <= 64 * 1024 && m >= 512) launch_stage2_ell<2>(P, ada, d_invperm, ncols, jbase, sym, gsplit, cleared);
+    else launch_stage2_ell<1>(P, ada, d_invperm, ncols, jbase, sym, gsplit, cleared);
+  } else {
     // z_j in LDS for the one-entry-per-work-item variant when the longest z_j fits 64 KB beside the block table
     const int64_t zl = (A.thread_per_row && A.zmaxj * 8 <= 64 * 1024) ? A.zmaxj : 0;
     const size_t lds = (size_t)A.sdpN * 8 + (size_t)zl * 8;

@@ -108,7 +108,7 @@ int sdm_plan_set_ada(sdm_plan *p, sdm_int N, sdm_int m, const sdm_int *Ajc, cons
   SDM_HIP_CHECK(hipSetDevice(p->device));
   if (!p->has_chol) throw std::runtime_error("sdm_plan_set_ada: call sdm_plan_set_chol first (it carries the ADA pattern)");
   if (m != p->chol.m) throw std::runtime_error("sdm_plan_set_ada: m mismatch");
-  ada_build(p, N, m, Ajc, Air, Apr, Ajc_psd, K->lpN, K->lorN, K->lorNL, K->sdpN, K->rsdpN, K->sdpNL, qblkstart,
+  ada_build(p, N, m, Ajc, Air, Apr, Ajc_psd, K->lpN, K->lorN, K->sdpN, K->rsdpN, K->sdpNL, qblkstart,
             psd_blkstart, Qjc, Qir, p->ada_jc.data(), p->ada_ir.data());
   // host copy of At for the operators of sdm_pcg.hip (their device tables are built on first use)
   p->ada.h_Ajc.assign(Ajc, Ajc + m + 1); p->ada.h_Air.assign(Air, Air + Ajc[m]); p->ada.h_Apr.assign(Apr, Apr + Ajc[m]);
@@ -624,7 +624,7 @@ void gw_build_getada1(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_in
   // Ajc2 is the end of the LP/Lorentz nonzeros)
   std::vector<sdm_int> Qjc(m + 1, 0);
   const sdm_int nlq = lorN > 0 ? qblkstart[lorN] : lpN;
-  ada_build(p, nlq, m, Ajc, Air, Apr, Ajc2, lpN, lorN, nullptr, 0, 0, nullptr, qblkstart, nullptr, Qjc.data(), nullptr, ADAjc, ADAir);
+  ada_build(p, nlq, m, Ajc, Air, Apr, Ajc2, lpN, lorN, 0, 0, nullptr, qblkstart, nullptr, Qjc.data(), nullptr, ADAjc, ADAir);
 }
 void gw_run_getada1(sdm_plan *p, const int *d_invperm, const double *dl, const double *ddet) {
   AdaPlan &A = p->ada;
@@ -638,7 +638,7 @@ bool gw_getada1_is_zero(sdm_plan *p) { return p->ada.nnz_lq == 0; }
 void gw_build_getada2(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int lorN, const sdm_int *Qjc, const sdm_int *Qir) {
   set_trivial_chol(p, m, ADAjc, ADAir);
   std::vector<sdm_int> Ajc(m + 1, 0), qb(lorN + 1, 0);
-  ada_build(p, lorN, m, Ajc.data(), nullptr, nullptr, Ajc.data(), 0, lorN, nullptr, 0, 0, nullptr, qb.data(), nullptr, Qjc, Qir, ADAjc, ADAir);
+  ada_build(p, lorN, m, Ajc.data(), nullptr, nullptr, Ajc.data(), 0, lorN, 0, 0, nullptr, qb.data(), nullptr, Qjc, Qir, ADAjc, ADAir);
 }
 void gw_run_getada2(sdm_plan *p, const int *d_invperm, const double *Qpr) {   // p->ada_val in/out
   if (p->ada.nnzQ) SDM_HIP_CHECK(hipMemcpyAsync(p->ada.qpr.p, Qpr, p->ada.nnzQ * sizeof(double), hipMemcpyHostToDevice, p->stream));
@@ -650,7 +650,7 @@ void gw_build_getada3(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_in
   std::vector<sdm_int> Qjc(m + 1, 0), qb(K->lorN + 1, 0);
   // the LP/Lorentz rows are not read by getada3: describe them as plain LP rows up to the first PSD row
   const sdm_int nlq = K->sdpN > 0 ? psd_blkstart[0] : N;
-  ada_build(p, N, m, Ajc, Air, Apr, Ajc1, nlq, 0, nullptr, K->sdpN, K->rsdpN, K->sdpNL, qb.data(), psd_blkstart, Qjc.data(), nullptr, ADAjc, ADAir);
+  ada_build(p, N, m, Ajc, Air, Apr, Ajc1, nlq, 0, K->sdpN, K->rsdpN, K->sdpNL, qb.data(), psd_blkstart, Qjc.data(), nullptr, ADAjc, ADAir);
 }
 void gw_run_getada3(sdm_plan *p, const double *udsqr, bool input_is_zero) {   // p->ada_val in/out, p->absd out
   // input_is_zero: the ADA' handed in is known to be the zero matrix (getada1 / getada2 had nothing to add): nothing to symmetrise
@@ -665,7 +665,7 @@ void gw_build_getada(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int
   const sdm_int nlq = lorN > 0 ? qblkstart[lorN] : lpN;             // = K.mainblks(3)-1: rows of Alq (getada.m:25)
   std::vector<sdm_int> ajc2(m), zq(m + 1, 0);
   for (sdm_int j = 0; j < m; j++) ajc2[j] = std::lower_bound(Air + Ajc[j], Air + Ajc[j + 1], nlq) - Air;
-  ada_build(p, nlq, m, Ajc, Air, Apr, ajc2.data(), lpN, lorN, nullptr, 0, 0, nullptr, qblkstart, nullptr,
+  ada_build(p, nlq, m, Ajc, Air, Apr, ajc2.data(), lpN, lorN, 0, 0, nullptr, qblkstart, nullptr,
             lorN > 0 ? Qjc : zq.data(), lorN > 0 ? Qir : nullptr, ADAjc, ADAir);
 }
 void gw_run_getada(sdm_plan *p, const double *dl, const double *ddet, const double *Qpr) {

@@ -315,7 +315,7 @@ struct AdaPlan {
   int64_t zmax = 0, zmaxj = 0;
   DevBuf<int64_t> c_zlen;
   DevBuf<int> g_row, g_len, g_bu;
-  DevBuf<long long> cdc64, cdp64;          // k_psd_stage2_ell: one record per column, by column / by ELL position (sdm_ada.hip, set-up)
+  DevBuf<long long> cdc64, cdp64;          // k_psd_stage2_ell: one record per column, by column / by ELL position (ell_column_records, sdm_ada_build.hip)
   DevBuf<int> cdc32, cdp32;
   DevBuf<int> d_Azpos, t_zdst;             // k_psd_stage2_ell: position in the full-length z vector of every PSD nonzero / of every task's block
   DevBuf<int> ell_pos;                     // constraint -> position in the ELL row order (its group = pos / 64)
@@ -378,10 +378,10 @@ struct sdm_plan {
   std::vector<hipGraphExec_t> graphs;   // captured launch sequences (sdm_plan_graph_*)
 };
 
-#define SDM_KLAUNCH_ON(P, st_, kernel, grid, block, shmem, ...)                           \
+#define SDM_KLAUNCH_AS(P, st_, name_, kernel, grid, block, shmem, ...)                    \
   do {                                                                                     \
     if ((P)->kprof.enabled) {                                                              \
-      sdm::KProf::Rec r_; r_.name = #kernel; r_.a = (P)->kprof.get(); r_.b = (P)->kprof.get(); \
+      sdm::KProf::Rec r_; r_.name = (name_); r_.a = (P)->kprof.get(); r_.b = (P)->kprof.get(); \
       SDM_HIP_CHECK(hipEventRecord(r_.a, (st_)));                                          \
       SDM_LAUNCH(kernel, grid, block, shmem, (st_), __VA_ARGS__);                          \
       SDM_HIP_CHECK(hipEventRecord(r_.b, (st_)));                                          \
@@ -390,7 +390,9 @@ struct sdm_plan {
       SDM_LAUNCH(kernel, grid, block, shmem, (st_), __VA_ARGS__);                          \
     }                                                                                      \
   } while (0)
+#define SDM_KLAUNCH_ON(P, st_, kernel, grid, block, shmem, ...) SDM_KLAUNCH_AS(P, st_, #kernel, kernel, grid, block, shmem, __VA_ARGS__)
 #define SDM_KLAUNCH(P, kernel, grid, block, shmem, ...) SDM_KLAUNCH_ON(P, (P)->stream, kernel, grid, block, shmem, __VA_ARGS__)
+// (SDM_KLAUNCH_AS: for a launch inside a function template, where the kernel is written with the template's parameter -- name_ is what kprof records)
 #ifdef SDM_EMU
 // (tests/hipemu only) a launch whose workgroups wait for each other, as one process per workgroup: emu_launch_concurrent
 #define SDM_KLAUNCH_CONCURRENT(P, kernel, grid, block, shmem, ...)                             \
@@ -510,11 +512,11 @@ void gw_build_getada(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int
                      sdm_int lpN, sdm_int lorN, const sdm_int *qblkstart, const sdm_int *Qjc, const sdm_int *Qir);
 void gw_run_getada(sdm_plan *p, const double *dl, const double *ddet, const double *Qpr);
 void gw_download(sdm_plan *p, double *ADApr, double *absd);
-// sdm_ada.hip
-void ada_build(sdm_plan *P, sdm_int N, sdm_int m, const sdm_int *Ajc, const sdm_int *Air, const double *Apr,
-               const sdm_int *Ajc_psd, sdm_int lpN, sdm_int lorN, const sdm_int *lorNL, sdm_int sdpN,
-               sdm_int rsdpN, const sdm_int *sdpNL, const sdm_int *qblkstart, const sdm_int *psd_blkstart,
+// sdm_ada_build.hip
+void ada_build(sdm_plan *P, sdm_int N, sdm_int m, const sdm_int *Ajc, const sdm_int *Air, const double *Apr, const sdm_int *Ajc_psd, sdm_int lpN,
+               sdm_int lorN, sdm_int sdpN, sdm_int rsdpN, const sdm_int *sdpNL, const sdm_int *qblkstart, const sdm_int *psd_blkstart,
                const sdm_int *Qjc, const sdm_int *Qir, const sdm_int *ADAjc, const sdm_int *ADAir);
+// sdm_ada.hip
 // mode bits: 1 = LP/Lorentz-det part (getada1), 2 = Lorentz rank-1 part (getada2), 4 = PSD part (getada3)
 // tri_perm (device, length m, inverse permutation) != nullptr -> only entries with invperm[i] <= invperm[j]
 // are touched (the reference's triangular bookkeeping); symmetrize -> spmakesym afterwards.
