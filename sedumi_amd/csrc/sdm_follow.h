@@ -1,15 +1,20 @@
-// sdm_follow.h -- device code shared by sdm_solve.hip (the inverses of the diagonal super-blocks) and sdm_chol.hip (whose one-launch
+// sdm_follow.h -- device code shared by sdm_solve_inv.hip (the inverses of the diagonal super-blocks) and sdm_chol.hip (whose one-launch
 // factor kernel carries the workgroups that build a front's inverse BEHIND its factorisation): matrix-core tile helpers, the 64x64
-// inversion, and the follower's body.  Device functions only; the kernels stay in their sources.
+// inversion, and the follower's body.  Device functions only; the kernels stay in their sources.  In front of them: what more than one
+// of the three units of the solves (sdm_solve_build.hip, sdm_solve_inv.hip, sdm_solve.hip) needs.
 #pragma once
 #include "sdm_plan.h"
 
 namespace sdm {
 
-constexpr int ST = 256;          // work-items per workgroup of every kernel of sdm_solve.hip
+constexpr int ST = 256;          // work-items per workgroup of every kernel of sdm_solve_inv.hip and sdm_solve.hip
 constexpr int TP = 65;           // LDS pitch of staged 64-wide operand blocks (conflict-free transposing stores)
 constexpr size_t INV_LDS = (size_t)4 * 64 * TP * sizeof(double);      // k_sinv128: four staged 64x64 blocks
 constexpr size_t TILE_LDS = (size_t)2 * 64 * TP * sizeof(double);     // k_stile / the follower: one A and one B operand block
+constexpr int SPREP_MAX_ITEMS = 256;                                  // k_sprep: one workgroup per item, all resident (one per CU)
+constexpr int MC_N = 32, MC_STRIDE = 32, MC_SET = MC_N * MC_STRIDE;   // counters of the merged sweep launches (merged_count, sdm_solve.hip)
+// offset of block Pb in a front's slice of LT (k_ltrans writes it, sfw_rows_body reads it: LT[r*W + c] = L((Pb+1) W + r, Pb W + c))
+__device__ __forceinline__ int64_t lt_boff(int ns, int W, int Pb) { return (int64_t)W * ((int64_t)Pb * ns - (int64_t)W * Pb * (Pb + 1) / 2); }
 
 // ================================================================ device helpers
 __device__ __forceinline__ double bits_to_double(unsigned long long u) { union { unsigned long long u; double d; } b; b.u = u; return b.d; }

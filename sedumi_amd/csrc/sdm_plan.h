@@ -150,7 +150,7 @@ struct LevelLaunch {
   int ride_wgs;         // workgroups of k_ldl_panel beyond workgroup 0 (row solves + pairs of update tiles), max over fronts
 };
 
-// one etree level of the solves (sdm_solve.hip)
+// one etree level of the solves (built by sdm_solve_build.hip, read by the sweeps of sdm_solve.hip)
 struct SolveLevel {
   int nfronts = 0, maxns = 0, maxms = 0, nsb = 0;   // nsb = super-blocks of the widest front
   bool children = false;                             // some front of the level has children (assembly launch needed)
@@ -194,7 +194,7 @@ struct CholPlan {
   HostFlag tmo;            // raised by a spin of THIS plan that gave up (chol_wait_timeouts): host[0] inside a launch of the factor (panel launches,
                            // k_ldl_front, the inverse behind it or solve_prepare's), host[1] inside a merged sweep launch (sweep_tmo)
   int *sweep_tmo() { return tmo.dev() + 1; }
-  // ---- solves (sdm_solve.hip): per front and super-block of sbw columns one nb x nb array in the arena S = the explicit
+  // ---- solves (planned by sdm_solve_build.hip, inverted by sdm_solve_inv.hip, applied by sdm_solve.hip): per front and super-block of sbw columns one nb x nb array in the arena S = the explicit
   // inverse of that diagonal block of L (block P of front s at sn_soff[s] + P * sbw * sn_sld[s], leading dimension sn_sld[s])
   int sbw = SBW_MIN;                 // super-block width of this plan (solve_build: covers the widest front, at most SBW_MAX)
   int sbw_req = 0;                   // != 0: width asked for through sdm_plan_set_solve_width (before set_chol)
@@ -212,7 +212,7 @@ struct CholPlan {
   std::vector<int64_t> sn_ltoff; DevBuf<int64_t> d_ltoff;
   DevBuf<int> l_lt; int n_lt = 0;    // 64x64 tiles of that transposition (4 ints each: s, P, I, J)
   DevBuf<double> Tarena;             // scratch of the inversion, same layout as S: T = B inv(A) of every combine step
-  DevBuf<int> sweep_cnt;             // counters of the merged sweep launches (two sets of MC_N, a 128-byte line each: sdm_solve.hip, merged_count)
+  DevBuf<int> sweep_cnt;             // counters of the merged sweep launches (two sets of MC_N, a 128-byte line each: sdm_follow.h; sdm_solve.hip, merged_count)
   DevBuf<unsigned long long> sb_g;   // per super-block: bit patterns of max|inverse| and max|L block| (growth check); behind them the counters of k_sprep
   DevBuf<int> l_i128, l_items;       // work lists of the inversion: 128-column leaves (4 ints each), combine tiles (8 ints each, sorted by stage)
   int n_i128 = 0, n_items = 0;
@@ -402,6 +402,16 @@ struct sdm_plan {
     SDM_LAUNCH_CONCURRENT(kernel, grid, block, shmem, __VA_ARGS__);                            \
     if ((P)->kprof.enabled) { SDM_HIP_CHECK(hipEventRecord(r_.b, (P)->stream)); (P)->kprof.recs.push_back(r_); } \
   } while (0)
+// a launch whose workgroups wait for each other's counters (k_sprep, the merged sweep launches): the emulator runs it as one process per
+// workgroup where the test asked for that (emu_concurrent) and the grid has at most `limit` workgroups, else -- and always on the device --
+// it is a plain SDM_KLAUNCH
+#define SDM_KLAUNCH_WAITING(P, limit, kernel, grid, block, shmem, ...)                         \
+  do {                                                                                         \
+    if (emu_concurrent() && (int)(grid).x <= (limit)) SDM_KLAUNCH_CONCURRENT(P, kernel, grid, block, shmem, __VA_ARGS__); \
+    else SDM_KLAUNCH(P, kernel, grid, block, shmem, __VA_ARGS__);                              \
+  } while (0)
+#else
+#define SDM_KLAUNCH_WAITING(P, limit, kernel, grid, block, shmem, ...) SDM_KLAUNCH(P, kernel, grid, block, shmem, __VA_ARGS__)
 #endif
 
 namespace sdm {
@@ -465,16 +475,19 @@ void chol_load_factor(sdm_plan *P, const double *h_Lpr, const double *h_d = null
 void vec_gather(sdm_plan *P, double *dst, const double *src, bool forward);  // dst[k]=src[perm[k]] / dst[perm[k]]=src[k]
 void vec_divd(sdm_plan *P, double *v);
 FrontTab front_tab(CholPlan &C);
-// sdm_solve.hip: inverse-block solves
+// sdm_solve_build.hip: inverse-block solves, planning
 void solve_build(sdm_plan *P);                      // host tables + buffers (end of chol_build)
+// sdm_solve_inv.hip: the inverses
 void solve_prepare(sdm_plan *P, bool sb_g_is_zero);  // after a factorisation: inverses of the diagonal super-blocks
 void solve_follow(sdm_plan *P, int level, hipStream_t st);   // the same for the fronts of a k_ldl_front level, launched NEXT to that kernel (CholPlan::follow)
+bool solve_follow_fits();                            // a workgroup of k_sinv_follow fits a compute unit of the current device (solve_build)
+void solve_stats(sdm_plan *P, sdm_int *nblocks, sdm_int *nbad, double *max_growth);
+// sdm_solve.hip: the sweeps
 const double *solve_d(sdm_plan *P);                  // the d the solves divide by: L.d (skipped pivots act as 1), or Ld of deninfac
 void solve_run(sdm_plan *P, const double *rhs, double *yout, int mode);   // mode bits 1 fw | 2 ./d | 4 bw
 // the fw, ./d, bw solve of solve_run(mode 7) level by level: what = 1 assembly launches of the forward sweep of levels l0 .. l1-1 only,
 // 2 their forward sweep without the assembly, 3 both, 4 the backward sweep of levels l1-1 down to l0
 void solve_levels(sdm_plan *P, int what, int l0, int l1);
-void solve_stats(sdm_plan *P, sdm_int *nblocks, sdm_int *nbad, double *max_growth);
 void solve_fw_batch(sdm_plan *P, const double *rhs, int64_t rhs_stride, double *y, int64_t y_stride, double *wv, int nrhs,
                     double *zdiv = nullptr, const double *dscale = nullptr, int l0 = 0, int l1 = -1, int what = 3);
 // sdm_pcg.hip: Amul / vecsym / psdscale on the plan

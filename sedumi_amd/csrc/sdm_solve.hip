@@ -1,17 +1,13 @@
 // sdm_solve.hip -- triangular solves  y = L \ b(perm),  y(perm) = L' \ b  (fwblkslv.c:77-134, bwblkslv.c:73-125)
-// for gfx950, built around EXPLICIT INVERSES of wide diagonal super-blocks.
+// for gfx950, built around EXPLICIT INVERSES of wide diagonal super-blocks: this file holds the SWEEPS that apply them.
 //
 // The reference substitutes column by column -- a chain of m dependent steps.  A single right-hand side leaves a
 // GPU nothing to batch over (the four solves of an IPM iteration depend on each other, wrapPcg.m:56-59), so the chain
 // itself has to go.  The columns of every front are cut into super-blocks of W = CholPlan::sbw columns (256 .. 2048:
 // the power of two that covers the widest front, so control07's 666-column front is ONE block and MAXCUT-4000's front
-// is two), and after every factorisation (solve_prepare) the diagonal block L_PP of every super-block is inverted
-// explicitly into the arena S:
-//   * 128-column leaves: 32x32 by substitution in registers, then two levels of  X21 = -inv(C) B inv(A)  on the FP64
-//     matrix cores, all inside one workgroup (k_sinv128);
-//   * combine levels 256, 512, ... W: the same identity on 64x64 product tiles (k_stile), two dependent stages per
-//     level (T = B inv(A), then X21 = -inv(C) T); small problems run all of it as ONE launch with completion
-//     counters between the stages (k_sprep).
+// is two; sdm_solve_build.hip plans the widths, the arenas and the per-level tables read here), and after every factorisation
+// the diagonal block L_PP of every super-block is inverted explicitly into the arena S (sdm_solve_inv.hip: solve_prepare,
+// solve_follow).
 // Then, per etree level and super-block P,
 //   forward   y_P = inv(L_PP) t_P                       one GEMV launch (k_sfw_diag), no dependency inside it,
 //             t_R -= L(R, P) y_P  for the rows R beyond  one GEMV launch (k_sfw_step), read from the factor itself
@@ -33,359 +29,7 @@
 
 namespace sdm {
 
-constexpr int SPREP_MAX_ITEMS = 256;                                  // k_sprep: one workgroup per item, all resident (one per CU)
-constexpr int MC_N = 32, MC_STRIDE = 32, MC_SET = MC_N * MC_STRIDE;   // counters of the merged sweep launches (merged_count below)
 constexpr int GRPW = 1024;       // columns (forward) / rows (backward) of a slab product in flight at a time: 32 16-byte loads per work-item
-
-// ---------------------------------------------------------------- host tables
-static void follow_decide(sdm_plan *P);
-#ifndef SDM_EMU
-__global__ void k_sinv_follow(const double *F, const double *DT, double *S, double *STr, FrontTab tab, const int *list, int *front_cnt, const int *diag_cnt,
-                              unsigned long long *sb_g, int *tmo);
-#endif
-void solve_build(sdm_plan *P) {
-  CholPlan &C = P->chol;
-  const int nsuper = (int)C.nsuper;
-  int W = C.sbw_req;
-  if (W == 0) { W = SBW_MIN; while (W < C.maxns && W < SBW_MAX) W *= 2; }
-  C.sbw = W;
-  // a new solve: no ill-conditioned block met yet (sweeps of the previous symbolic factor still in flight would write their notes
-  // after this reset: drained first -- set_chol happens once per solve)
-  if (C.noted.host) SDM_HIP_CHECK(hipStreamSynchronize(P->stream));
-  C.noted.ensure(); C.noted.host[0] = C.noted.host[1] = 0; C.refine_on = false; C.sweep_seq = 0;
-  C.sn_soff.assign(nsuper, 0); C.sn_sld.assign(nsuper, 0); C.sn_sboff.assign(nsuper, 0);
-  std::vector<int> i128;
-  std::vector<std::vector<int>> stage(2 * SINV_MAXLEV);              // combine tiles per stage st = 2 * level + (0: T, 1: X)
-  std::vector<std::vector<int>> stage_w(2 * SINV_MAXLEV);            // and the number of K steps of each
-  int64_t soff = 0; int sb = 0;
-  for (int s = 0; s < nsuper; s++) {
-    const int ns = C.sn_ns[s];
-    // leading dimension of the front's inverse blocks: a multiple of 16 (whole 128-byte lines per 16-row slab), never a
-    // multiple of 256 doubles (columns 2 KB-aligned to each other would land on the same memory channels)
-    int sld = (std::min(ns, W) + 15) & ~15;
-    if (sld % 256 == 0) sld += 16;
-    C.sn_soff[s] = soff; C.sn_sld[s] = sld; C.sn_sboff[s] = sb;
-    soff += (int64_t)sld * ns;
-    const int nsb = (ns + W - 1) / W;
-    const bool act = C.sn_active.empty() || C.sn_active[s] != 0;     // (supernodes of other ranks: a place in the arena, no work)
-    for (int h = 0; act && 128 * h < ns; h++) { i128.push_back(s); i128.push_back(h); i128.push_back(0); i128.push_back(0); }
-    for (int Pb = 0; act && Pb < nsb; Pb++) {
-      const int nb = std::min(W, ns - Pb * W);
-      int prev = (nb + 127) / 128;                                    // what stage 0 waits for: the leaves of this super-block
-      for (int lev = 0; lev < SINV_MAXLEV; lev++) {
-        const int h = 128 << lev;
-        if (h >= nb) break;
-        int cnt = 0;
-        for (int t = 0; t < 2; t++) {
-          std::vector<int> &dst = stage[2 * lev + t];
-          for (int pi = 0; pi * 2 * h + h < nb; pi++) {
-            const int nc = std::min(h, nb - pi * 2 * h - h);
-            for (int I = 0; 64 * I < nc; I++)
-              for (int J = 0; 64 * J < h; J++) {
-                const int it[8] = {s, Pb, lev, pi, I, J, t, prev};
-                dst.insert(dst.end(), it, it + 8);
-                stage_w[2 * lev + t].push_back(t == 0 ? h / 64 - J : std::min(I + 1, (nc + 63) / 64));   // its K steps (stile_body)
-                if (t == 0) cnt++;
-              }
-          }
-          prev = cnt;                                                  // T and X stages of a level have the same tiles
-        }
-      }
-    }
-    sb += nsb;
-  }
-  C.ssize = soff; C.nsbtot = sb;
-  std::vector<int> items;
-  C.stage_ptr.assign(2 * SINV_MAXLEV + 1, 0);
-  for (int st = 0; st < 2 * SINV_MAXLEV; st++) {
-    C.stage_ptr[st] = (int)items.size() / 8;
-    // Longest items first.  The products are triangular (1 .. h/64 K steps per tile) and a launch of more tiles than fit the device
-    // at once lasts as long as whatever is dispatched last: in the order the tiles are generated (long ones last in stage X) the two
-    // 496-tile stages of MAXCUT-4000 took 107 and 103 us, sorted 90 and 89 (profiles/r07_inverse_tile_variants.txt).  Measured and
-    // not kept: workgroups taking the tiles in pairs, longest with shortest (88 us, and the small stages slower: a workgroup alone on
-    // its CU needs 4.6 us per K step, two on a CU 6.4 us each), and operand blocks two K steps ahead in registers (a few us, at the
-    // price of the second workgroup per CU) -- a K step is 64 KB of operands at the ~16 GB/s a CU gets when all CUs stream.
-    const std::vector<int> &w = stage_w[st];
-    std::vector<int> ord(w.size());
-    for (size_t i = 0; i < ord.size(); i++) ord[i] = (int)i;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return w[a] > w[b]; });
-    for (int i : ord) items.insert(items.end(), stage[st].begin() + 8 * (size_t)i, stage[st].begin() + 8 * (size_t)i + 8);
-  }
-  C.stage_ptr[2 * SINV_MAXLEV] = (int)items.size() / 8;
-  C.n_i128 = (int)i128.size() / 4; C.n_items = (int)items.size() / 8;
-  C.l_i128.upload(i128); C.l_items.upload(items);
-  C.d_soff.upload(C.sn_soff); C.d_sld.upload(C.sn_sld); C.d_sboff.upload(C.sn_sboff);
-  const size_t sz = (size_t)std::max<int64_t>(soff, 1);
-  C.S.alloc(sz); C.ST.alloc(sz); C.Tarena.alloc(C.n_items ? sz : 1);
-  SDM_HIP_CHECK(hipMemset(C.S.p, 0, sz * sizeof(double)));            // upper triangles stay zero for good
-  SDM_HIP_CHECK(hipMemset(C.ST.p, 0, sz * sizeof(double)));           // (here: the lower ones)
-  // fronts of several super-blocks: transposed copy of the rows of L below each super-block (forward step launches)
-  {
-    C.sn_ltoff.assign(nsuper, 0);
-    std::vector<int> lt;
-    int64_t ltoff = 0;
-    for (int s = 0; s < nsuper; s++) {
-      const int ns = C.sn_ns[s], nsb = (ns + W - 1) / W;
-      C.sn_ltoff[s] = ltoff;
-      if (!(C.sn_active.empty() || C.sn_active[s] != 0)) continue;
-      for (int Pb = 0; Pb + 1 < nsb; Pb++) {
-        const int nr = ns - (Pb + 1) * W;
-        for (int I = 0; 64 * I < nr; I++)
-          for (int J = 0; 64 * J < W; J++) { lt.push_back(s); lt.push_back(Pb); lt.push_back(I); lt.push_back(J); }
-        ltoff += (int64_t)nr * W;
-      }
-    }
-    C.n_lt = (int)lt.size() / 4;
-    C.l_lt.upload(lt); C.d_ltoff.upload(C.sn_ltoff);
-    C.LT.alloc((size_t)std::max<int64_t>(ltoff, 1));
-  }
-  C.xfin.alloc((size_t)std::max<sdm_int>(C.m, 1)); C.zdiv.alloc((size_t)std::max<sdm_int>(C.m, 1));
-  // growth records (2 words per super-block), then the completion counters of k_sprep (SPREP_NCNT ints per super-block)
-  const size_t gw = (size_t)std::max(sb, 1) * (2 + SPREP_NCNT / 2);
-  C.sb_g.alloc(gw);
-  SDM_HIP_CHECK(hipMemset(C.sb_g.p, 0, gw * sizeof(unsigned long long)));
-  C.sweep_cnt.alloc(2 * MC_SET);                                    // (the merged sweep launches' counters: merged_count)
-  SDM_HIP_CHECK(hipMemset(C.sweep_cnt.p, 0, 2 * MC_SET * sizeof(int)));
-  // levels
-  C.slev.assign(C.nlevels, SolveLevel());
-  for (int l = 0; l < C.nlevels; l++) {
-    SolveLevel &L = C.slev[l];
-    L.nfronts = C.levptr[l + 1] - C.levptr[l];
-    for (int i = C.levptr[l]; i < C.levptr[l + 1]; i++) {
-      const int s = C.levlist[i], ns = C.sn_ns[s], ms = C.sn_ms[s];
-      L.maxns = std::max(L.maxns, ns); L.maxms = std::max(L.maxms, ms);
-      if (C.childptr[s + 1] > C.childptr[s]) L.children = true;
-      if (ms > ns) L.below = true;
-    }
-    L.nsb = (L.maxns + W - 1) / W;
-    L.slabs_fw.assign(L.nsb, 0);
-    for (int i = C.levptr[l]; i < C.levptr[l + 1]; i++) {
-      const int s = C.levlist[i], ns = C.sn_ns[s], ms = C.sn_ms[s];
-      for (int Pb = 0; Pb * W < ns; Pb++)                              // (slabs of the rows BELOW the supernode; its own later rows: k_sfw_rows)
-        if (ms > ns) L.slabs_fw[Pb] = std::max(L.slabs_fw[Pb], (ms - (ns & ~1) + SROWS - 1) / SROWS);
-    }
-  }
-  follow_decide(P);
-}
-
-// Can the inverses be built BEHIND the factorisation (k_sinv_follow)?  Every level must be a k_ldl_front level, every front
-// one super-block, and the workgroups of both kernels of a level must fit the device together, one per compute unit
-// (whichever of the two the hardware dispatches first, nobody may be kept out by workgroups that wait).
-static void follow_decide(sdm_plan *P) {
-  CholPlan &C = P->chol;
-  C.follow = false;
-  C.lev_followT.assign(C.nlevels, 0);
-  if (C.nlevels == 0 || C.maxns > C.sbw || C.front_disabled) return;
-  int ncu = 1 << 20;
-#ifndef SDM_EMU
-  SDM_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, P->device));
-  {
-    // (one workgroup of either kernel per compute unit is what the count below assumes: the follower must fit at least that)
-    int per_cu = 0;
-    SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_sinv_follow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TILE_LDS));
-    SDM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_sinv_follow, ST, TILE_LDS));
-    if (per_cu < 1) return;
-  }
-#endif
-  for (int l = 0; l < C.nlevels; l++) {
-    if (!C.lev_persist[l]) return;
-    const int nfr = C.levptr[l + 1] - C.levptr[l];
-    int Tn = 0;
-    for (int i = C.levptr[l]; i < C.levptr[l + 1]; i++) Tn = std::max(Tn, (C.sn_ns[C.levlist[i]] + 63) / 64);
-    C.lev_followT[l] = Tn * (Tn + 1) / 2;
-    if ((int64_t)nfr * (C.lev_followT[l] + C.lev_maxT[l] + C.lev_ntw[l]) > ncu - ncu / 8) return;
-  }
-  C.follow = true;
-}
-
-// Leaves.  One workgroup per 128-column block h of a front, bottom-up, everything in LDS / registers:
-//   32x32  each of the four wavefronts inverts one 32x32 unit lower triangular diagonal block by columns (lane j owns
-//          column j of the inverse in registers; the entries of L come as broadcast LDS reads at compile-time offsets);
-//   64x64  X10 = -inv(A11) (A10 inv(A00)) for the two 64-column blocks A and C (matrix cores, two wavefronts each);
-//   128    X21 = -inv(C) (B inv(A)) on the FP64 matrix cores, B = L(C rows, A columns) requested at the very start.
-// Results go to S; max|inv| and max|L| to sb_g (growth check).
-template <bool WT>
-__device__ __forceinline__ void sinv128_body(char *smem, const double *__restrict__ F, double *__restrict__ S, double *__restrict__ STr, const FrontTab &tab,
-                                             const int *it, unsigned long long *sb_g, int W) {
-  double *bufA = (double *)smem, *bufC = bufA + 64 * TP, *bufB = bufC + 64 * TP, *bufT = bufB + 64 * TP;
-  const int s = it[0], h = it[1];
-  const int ns = tab.ns[s], ld = tab.ld[s], sld = tab.sld[s];
-  const double *Fs = F + tab.foff[s];
-  const int k0 = 128 * h, nbA = min(64, ns - k0), nbC = max(0, min(64, ns - k0 - 64));
-  const int Pb = k0 / W, kl = k0 - Pb * W;                          // super-block of the leaf, its first column inside it
-  double *Ss = S + tab.soff[s] + (int64_t)Pb * W * sld;
-  double *Ts = STr + tab.soff[s] + (int64_t)Pb * W * sld;           // the transposed copy: Ts[r*sld + c] = inverse(r, c)
-  unsigned long long *gP = sb_g + 2 * (tab.sboff[s] + Pb);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  double vB[SPT];
-  SDM_PHASE_BEGIN();
-  if (nbC > 0) stage_colmajor_load(vB, Fs + (int64_t)k0 * ld + k0 + 64, ld, nbC, 64, tid);     // B(row, k) = L(k0+64+row, k0+k)
-  // raw strictly lower triangles, column-major: rawA[k*TP + i] = L(k0+i, k0+k) (bufT), rawC likewise (bufB); the
-  // destination buffers start as zero
-  double *rawA = bufT, *rawC = bufB;
-  double lmx = 0.0;
-  {
-    double va[SPT], vc[SPT];
-    const int i = tid & 63, kq = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < SPT; j++) {
-      const int k = kq + (ST / 64) * j;
-      va[j] = Fs[(int64_t)(k0 + min(k, nbA - 1)) * ld + k0 + min(i, nbA - 1)];
-      vc[j] = nbC > 0 ? Fs[(int64_t)(k0 + 64 + min(k, nbC - 1)) * ld + k0 + 64 + min(i, nbC - 1)] : 0.0;
-    }
-#pragma unroll
-    for (int j = 0; j < SPT; j++) {
-      const int k = kq + (ST / 64) * j;
-      const double a = (i > k && i < nbA) ? va[j] : 0.0, c = (i > k && i < nbC) ? vc[j] : 0.0;
-      rawA[k * TP + i] = a; rawC[k * TP + i] = c;
-      bufA[k * TP + i] = 0.0; bufC[k * TP + i] = 0.0;
-      lmx = fmax(lmx, fmax(fabs(a), fabs(c)));
-    }
-  }
-  __syncthreads();
-  SDM_PHASE(0);
-  inv64_pair(rawA, rawC, bufA, bufC, wave, lane, gP);
-  SDM_PHASE(3);
-  __syncthreads();                                                  // bufA = inv(A) (B operand), bufC = inv(C) (A operand); raw buffers free
-  if (nbC > 0) lmx = fmax(lmx, stage_colmajor_store(bufB, vB, nbC, 64, tid));
-  wave_atomic_max(gP + 1, lmx, lane);
-  // inverses to S (lower triangles incl. the unit diagonal; the upper triangles of S are zero and stay zero)
-  for (int e = tid; e < 64 * 64; e += ST) {
-    const int i = e & 63, j = e >> 6;
-    if (i >= j && i < nbA) { if (WT) sdm_store_wt(&Ss[(int64_t)(kl + j) * sld + kl + i], bufA[i * TP + j]); else Ss[(int64_t)(kl + j) * sld + kl + i] = bufA[i * TP + j]; }
-    if (i >= j && i < nbC) { if (WT) sdm_store_wt(&Ss[(int64_t)(kl + 64 + j) * sld + kl + 64 + i], bufC[j * TP + i]); else Ss[(int64_t)(kl + 64 + j) * sld + kl + 64 + i] = bufC[j * TP + i]; }
-  }
-  for (int e = tid; e < 64 * 64; e += ST) {                           // transposed copy: consecutive work-items on consecutive columns j
-    const int j = e & 63, i = e >> 6;
-    if (i >= j && i < nbA) { if (WT) sdm_store_wt(&Ts[(int64_t)(kl + i) * sld + kl + j], bufA[i * TP + j]); else Ts[(int64_t)(kl + i) * sld + kl + j] = bufA[i * TP + j]; }
-    if (i >= j && i < nbC) { if (WT) sdm_store_wt(&Ts[(int64_t)(kl + 64 + i) * sld + kl + 64 + j], bufC[j * TP + i]); else Ts[(int64_t)(kl + 64 + i) * sld + kl + 64 + j] = bufC[j * TP + i]; }
-  }
-  SDM_PHASE(4);
-  if (nbC <= 0) return;
-  __syncthreads();
-  Acc22 acc;
-  acc_zero(acc);
-  mma_block(acc, bufB, bufA, wave, lane);                           // T = B inv(A)
-  acc_to_lds_rowmajor(acc, bufT, wave, lane, 1.0);                  // bufT[k*TP + col] = T(k, col): a B operand
-  __syncthreads();
-  acc_zero(acc);
-  mma_block(acc, bufC, bufT, wave, lane);                           // inv(C) T
-  __syncthreads();                                                  // bufB is free: stage the result for coalesced stores
-  acc_to_lds_rowmajor(acc, bufB, wave, lane, -1.0);
-  __syncthreads();
-  SDM_PHASE(5);
-  const double gm = store_tile<WT>(Ss + (int64_t)kl * sld + kl + 64, sld, bufB, nbC, 64, tid);
-  store_tile_T<WT>(Ts + (int64_t)(kl + 64) * sld + kl, sld, bufB, nbC, 64, tid);
-  wave_atomic_max(gP, gm, lane);
-  SDM_PHASE(6);
-}
-__global__ void __launch_bounds__(ST)
-k_sinv128(const double *__restrict__ F, double *__restrict__ S, double *__restrict__ STr, FrontTab tab, const int *items, unsigned long long *sb_g, int W) {
-  SDM_DYN_SMEM(smem);
-  sinv128_body<false>(smem, F, S, STr, tab, items + 4 * blockIdx.x, sb_g, W);
-}
-
-// Combine levels.  Level lev joins the inverses of neighbouring column ranges of half width h = 128 << lev inside a
-// super-block:  inv([A 0; B C]) = [inv(A) 0; -inv(C) B inv(A), inv(C)]  with A = columns a0 .. a0+h-1, C = the nc <= h
-// columns behind them.  One 64x64 tile of one of the two products per item {s, Pb, lev, pair, I, J, stage, wait}:
-//   stage 0  T(I, J)   =   sum_{K >= J} B(I, K) inv(A)(K, J)        B = L(C rows, A columns) from the factor; T into the scratch arena
-//   stage 1  X21(I, J) = - sum_{K <= I} inv(C)(I, K) T(K, J)        into S
-// (both triangular in K: only the 64-blocks that can be non-zero are multiplied).
-template <bool WT>
-__device__ __forceinline__ void stile_body(char *smem, const double *F, double *S, double *STr, double *T, const FrontTab &tab, const int *it,
-                                           unsigned long long *sb_g, int W) {
-  double *As = (double *)smem, *Bs = As + 64 * TP;
-  const int s = it[0], Pb = it[1], lev = it[2], pi = it[3], I = it[4], J = it[5], stage = it[6];
-  const int ns = tab.ns[s], ld = tab.ld[s], sld = tab.sld[s];
-  const int P0 = Pb * W, nb = min(W, ns - P0);
-  const int h = 128 << lev, a0 = pi * 2 * h, nc = min(h, nb - a0 - h);
-  const double *Fs = F + tab.foff[s];
-  double *Sb = S + tab.soff[s] + (int64_t)P0 * sld, *Tb = T + tab.soff[s] + (int64_t)P0 * sld;
-  unsigned long long *gP = sb_g + 2 * (tab.sboff[s] + Pb);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const double *Ap, *Bp; double *Cp;
-  int64_t lda, ldb;
-  const int arows = min(64, nc - 64 * I);
-  int kvalid;
-  if (stage == 0) {
-    kvalid = h - 64 * J;
-    Ap = Fs + (int64_t)(P0 + a0 + 64 * J) * ld + P0 + a0 + h + 64 * I; lda = ld;
-    Bp = Sb + (int64_t)(a0 + 64 * J) * sld + a0 + 64 * J; ldb = sld;
-    Cp = Tb + (int64_t)(a0 + 64 * J) * sld + a0 + h + 64 * I;
-  } else {
-    kvalid = min(64 * (I + 1), nc);
-    Ap = Sb + (int64_t)(a0 + h) * sld + a0 + h + 64 * I; lda = sld;
-    Bp = Tb + (int64_t)(a0 + 64 * J) * sld + a0 + h; ldb = sld;
-    Cp = Sb + (int64_t)(a0 + 64 * J) * sld + a0 + h + 64 * I;
-  }
-  Acc22 acc;
-  acc_zero(acc);
-  double lmx = 0.0;
-  double va[SPT], vb[SPT];
-  SDM_PHASE_BEGIN();
-  stage_colmajor_load<WT>(va, Ap, lda, arows, kvalid, tid);
-  stage_transposed_load<WT>(vb, Bp, ldb, kvalid, 64, tid);
-  for (int kb = 0; kb < kvalid; kb += 64) {
-    lmx = fmax(lmx, stage_colmajor_store(As, va, arows, kvalid - kb, tid));
-    stage_transposed_store(Bs, vb, kvalid - kb, 64, tid);
-    __syncthreads();
-    if (kb + 64 < kvalid) {                                          // next K block: loads in flight during the products
-      stage_colmajor_load<WT>(va, Ap + (int64_t)(kb + 64) * lda, lda, arows, kvalid - kb - 64, tid);
-      stage_transposed_load<WT>(vb, Bp + kb + 64, ldb, kvalid - kb - 64, 64, tid);
-    }
-    mma_block(acc, As, Bs, wave, lane);
-    __syncthreads();
-  }
-  SDM_PHASE(8 + 4 * stage);
-  if (stage == 0) wave_atomic_max(gP + 1, lmx, lane);                // max |L| over the off-diagonal blocks of the super-block
-  acc_to_lds_rowmajor(acc, As, wave, lane, stage == 0 ? 1.0 : -1.0);
-  __syncthreads();
-  const double gm = store_tile<WT>(Cp, sld, As, arows, 64, tid);
-  if (stage == 1) {
-    store_tile_T<WT>(STr + tab.soff[s] + (int64_t)P0 * sld + (int64_t)(a0 + h + 64 * I) * sld + a0 + 64 * J, sld, As, arows, 64, tid);
-    wave_atomic_max(gP, gm, lane);                                   // max |inverse|
-  }
-  SDM_PHASE(9 + 4 * stage);
-}
-__global__ void __launch_bounds__(ST)
-k_stile(const double *F, double *S, double *STr, double *T, FrontTab tab, const int *items, unsigned long long *sb_g, int W) {
-  SDM_DYN_SMEM(smem);
-  stile_body<false>(smem, F, S, STr, T, tab, items + 8 * blockIdx.x, sb_g, W);
-}
-
-// ---- all of the above in ONE launch for problems whose items fit the device at once (k_sprep): workgroups take the
-// items in the order leaves, level 0 stage T, level 0 stage X, level 1 stage T, ... and wait on per-super-block completion
-// counters instead of on launch boundaries.  Producers store write-through and count after their stores are
-// acknowledged; consumers poll relaxed and read with sc1 loads.
-// cnt[SPREP_NCNT * sb + 0] = finished leaves, [1 + st] = finished tiles of stage st (zeroed with sb_g by k_prep_pivots).
-__global__ void __launch_bounds__(ST)
-k_sprep(const double *F, double *S, double *STr, double *T, FrontTab tab, const int *l_i128, int n_i128, const int *l_items,
-        unsigned long long *sb_g, int *cnt, int W, int *tmo) {
-  SDM_DYN_SMEM(smem);
-  const int b = blockIdx.x;
-  if (b < n_i128) {
-    const int *it = l_i128 + 4 * b;
-    sinv128_body<true>(smem, F, S, STr, tab, it, sb_g, W);
-    prep_done(cnt + SPREP_NCNT * (tab.sboff[it[0]] + (128 * it[1]) / W));
-    return;
-  }
-  const int *it = l_items + 8 * (b - n_i128);
-  const int st = 2 * it[2] + it[6];
-  int *c = cnt + SPREP_NCNT * (tab.sboff[it[0]] + it[1]);
-  prep_wait(c + st, it[7], tmo);
-  stile_body<true>(smem, F, S, STr, T, tab, it, sb_g, W);
-  prep_done(c + st + 1);
-}
-
-// ---- the inverse of a whole front BEHIND its factorisation: the body is sinv_follow_body (sdm_follow.h); this kernel runs it where
-// the k_ldl_front launch does not carry the follower's workgroups itself (the emulator; captured graphs of older plans)
-__global__ void __launch_bounds__(ST)
-k_sinv_follow(const double *F, const double *DT, double *S, double *STr, FrontTab tab, const int *list, int *front_cnt, const int *diag_cnt,
-              unsigned long long *sb_g, int *tmo) {
-  SDM_DYN_SMEM(smem);
-  const FollowDesc fd = follow_desc(tab, list, (int)blockIdx.y);
-  sinv_follow_body(smem, (int)blockIdx.x, fd, F, DT, S, STr, front_cnt, diag_cnt, sb_g, tmo);
-}
 
 // ================================================================ substitution fallback for one super-block
 // Rare path (growth check failed): L_PP y = r  /  L_PP' x = v  in place on the nb entries w (LDS) by ONE workgroup.
@@ -656,29 +300,16 @@ __device__ __forceinline__ void tri_task(int nb, int b, int wave, int &t, int &s
   else { t = n1 + 2 * (b - wg1) + (wave >> 1); seg = wave & 1; nseg = 2; if (t >= nb) t = -1; }
 }
 __host__ __device__ inline int tri_grid(int nb) { const int n1 = nb < SEGN ? nb : SEGN; return (n1 + 3) / 4 + (nb - n1 + 1) / 2; }
+// (host) grid.x of a diagonal-block launch over blocks of up to nb columns, and the workgroups that n rows (forward) or columns (backward) of
+// the row launches take at width W: two per workgroup when W > SEGN, else four (sfw_rows_body, sbw_step_body)
+static inline int diag_grid(int nb, int W) { return W <= 256 ? (nb + 15) / 16 : tri_grid(nb); }
+static inline int row_wgs(int n, int W) { return W > SEGN ? (n + 1) / 2 : (n + 3) / 4; }
 // the two partial sums of a split row -> its first wavefront (every wavefront of the workgroup calls this)
 __device__ __forceinline__ double seg_combine(double *part, double a, int wave, int lane, int nseg) {
   if (nseg == 1) return a;                                            // (uniform for the workgroup)
   if (lane == 0) part[wave] = a;
   __syncthreads();
   return part[wave & ~1] + part[wave | 1];
-}
-// transposed copy of the rows of L below super-block Pb of a front (64x64 tiles through LDS): LT[r*W + c] = L((Pb+1) W + r, Pb W + c)
-__device__ __forceinline__ int64_t lt_boff(int ns, int W, int Pb) { return (int64_t)W * ((int64_t)Pb * ns - (int64_t)W * Pb * (Pb + 1) / 2); }
-__global__ void __launch_bounds__(ST)
-k_ltrans(const double *__restrict__ F, double *__restrict__ LT, FrontTab tab, const int *items, int W) {
-  __shared__ double t[64][65];
-  const int *it = items + 4 * blockIdx.x;
-  const int s = it[0], Pb = it[1], I = it[2], J = it[3];
-  const int ns = tab.ns[s], ld = tab.ld[s];
-  const int R0 = (Pb + 1) * W, nr = ns - R0;
-  const double *src = F + tab.foff[s] + (int64_t)(Pb * W + 64 * J) * ld + R0 + 64 * I;       // (row i, column c) at src[c*ld + i]
-  double *dst = LT + tab.ltoff[s] + lt_boff(ns, W, Pb) + (int64_t)(64 * I) * W + 64 * J;
-  const int tid = threadIdx.x, a = tid & 63, b = tid >> 6;
-  const int nri = min(64, nr - 64 * I);
-  for (int c = b; c < 64; c += ST / 64) t[c][a] = a < nri ? src[(int64_t)c * ld + a] : 0.0;
-  __syncthreads();
-  for (int i = b; i < 64; i += ST / 64) if (i < nri) dst[(int64_t)i * W + a] = t[a][i];
 }
 
 // ================================================================ forward sweep
@@ -1243,74 +874,6 @@ static FrontTab level_tab(const CholPlan &C, FrontTab t, int l) {
   t.o_xl = C.sn_xl[s];
   return t;
 }
-static void solve_attrs() {
-#ifndef SDM_EMU
-  static bool attr = false;
-  if (!attr) {
-    SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_sinv128, hipFuncAttributeMaxDynamicSharedMemorySize, (int)INV_LDS));
-    SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_stile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TILE_LDS));
-    SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_sprep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)INV_LDS));
-    SDM_HIP_CHECK(hipFuncSetAttribute((const void *)k_sinv_follow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TILE_LDS));
-    attr = true;
-  }
-#endif
-}
-// the inverses of the fronts of level l behind their factorisation: launched on stream st right after (next to) k_ldl_front
-void solve_follow(sdm_plan *P, int l, hipStream_t st) {
-  CholPlan &C = P->chol;
-  solve_attrs();
-  C.growth_used = C.growth_max;
-  const int nfr = C.levptr[l + 1] - C.levptr[l];
-  SDM_KLAUNCH_ON(P, st, k_sinv_follow, dim3(C.lev_followT[l], nfr), dim3(ST), TILE_LDS, C.fronts.p, C.frontsT.p, C.S.p, C.ST.p, front_tab(C),
-                 C.d_levlist.p + C.levptr[l], C.front_cnt.p, C.diag_cnt.p, C.sb_g.p, C.tmo.dev());
-}
-void solve_prepare(sdm_plan *P, bool sb_g_is_zero) {
-  CholPlan &C = P->chol;
-  FrontTab tab = front_tab(C);
-  solve_attrs();
-  C.growth_used = C.growth_max;                                     // the solves decide with the bound in force here
-  const size_t gw = (size_t)std::max(C.nsbtot, 1) * (2 + SPREP_NCNT / 2);
-  if (!sb_g_is_zero)                                                // (a factorisation zeroes them in k_prep_pivots)
-    SDM_HIP_CHECK(hipMemsetAsync(C.sb_g.p, 0, gw * sizeof(unsigned long long), P->stream));
-  const int W = C.sbw;
-  if (C.n_lt) SDM_KLAUNCH(P, k_ltrans, dim3(C.n_lt), dim3(ST), 0, C.fronts.p, C.LT.p, tab, C.l_lt.p, W);
-  if (C.n_i128 == 0) return;
-  if (C.n_i128 + C.n_items <= SPREP_MAX_ITEMS && !C.sprep_off) {    // everything resident at once: one launch, counters instead of boundaries
-#ifdef SDM_EMU
-    if (emu_concurrent() && C.n_i128 + C.n_items <= 200) {          // as on the device: its workgroups wait for each other's counters (one process each)
-      SDM_KLAUNCH_CONCURRENT(P, k_sprep, dim3(C.n_i128 + C.n_items), dim3(ST), INV_LDS, C.fronts.p, C.S.p, C.ST.p, C.Tarena.p, tab, C.l_i128.p, C.n_i128,
-                             C.l_items.p, C.sb_g.p, (int *)(C.sb_g.p + 2 * std::max(C.nsbtot, 1)), W, C.tmo.dev());
-      return;
-    }
-#endif
-    SDM_KLAUNCH(P, k_sprep, dim3(C.n_i128 + C.n_items), dim3(ST), INV_LDS, C.fronts.p, C.S.p, C.ST.p, C.Tarena.p, tab, C.l_i128.p, C.n_i128,
-                C.l_items.p, C.sb_g.p, (int *)(C.sb_g.p + 2 * std::max(C.nsbtot, 1)), W, C.tmo.dev());
-    return;
-  }
-  SDM_KLAUNCH(P, k_sinv128, dim3(C.n_i128), dim3(ST), INV_LDS, C.fronts.p, C.S.p, C.ST.p, tab, C.l_i128.p, C.sb_g.p, W);
-  for (int st = 0; st < 2 * SINV_MAXLEV; st++) {
-    const int n = C.stage_ptr[st + 1] - C.stage_ptr[st];
-    if (n > 0) SDM_KLAUNCH(P, k_stile, dim3(n), dim3(ST), TILE_LDS, C.fronts.p, C.S.p, C.ST.p, C.Tarena.p, tab, C.l_items.p + 8 * (size_t)C.stage_ptr[st], C.sb_g.p, W);
-  }
-}
-
-// growth statistics of the last solve_prepare (host read-back; tests and bench reporting)
-void solve_stats(sdm_plan *P, sdm_int *nblocks, sdm_int *nbad, double *max_growth) {
-  CholPlan &C = P->chol;
-  std::vector<unsigned long long> g((size_t)std::max(2 * C.nsbtot, 2));
-  SDM_HIP_CHECK(hipStreamSynchronize(P->stream));
-  SDM_HIP_CHECK(hipMemcpy(g.data(), C.sb_g.p, g.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  sdm_int bad = 0; double mx = 0.0;
-  for (int i = 0; i < C.nsbtot; i++) {
-    union { unsigned long long u; double d; } a, b; a.u = g[2 * i]; b.u = g[2 * i + 1];
-    const double gr = a.d * b.d;
-    if (!(gr <= C.growth_used)) bad++;
-    if (gr > mx || gr != gr) mx = gr;
-  }
-  if (nblocks) *nblocks = C.nsbtot;
-  if (nbad) *nbad = bad;
-  if (max_growth) *max_growth = mx;
-}
 
 // do the sweeps run the refinement launches for blocks beyond the growth bound?  (CholPlan::refine_mode; the note is read as it is
 // now, without waiting for the device)
@@ -1322,14 +885,20 @@ static int sweep_merge_level(const CholPlan &C) {
   const char *e = getenv("SEDUMI_HIP_SWEEP_MERGE");               // (read per sweep: the tests switch it)
   return e ? atoi(e) : 1;
 }
-#ifdef SDM_EMU
 // (tests, emulator build only) the next n merged sweep launches report a time-out, as if one of their workgroups had given up waiting: a
 // counter of its own, apart from the factor's (emu_inject_timeouts), so that neither kind of launch takes the other's.  Returns the
 // injections still pending before the call.
+#ifdef SDM_EMU
 static int g_sweep_timeouts = 0;
 extern "C" int sdm_emu_inject_sweep_timeouts(int n) { const int left = g_sweep_timeouts; g_sweep_timeouts = n; return left; }
 static void emu_sweep_timeout(CholPlan &C) { if (g_sweep_timeouts > 0) { g_sweep_timeouts--; ((volatile int *)C.tmo.host)[1] = 1; } }
+#else
+static inline void emu_sweep_timeout(CholPlan &) {}
 #endif
+// a merged sweep launch of nwg workgroups (tests/test_emu_concurrent.py: one process per workgroup, the diagonal role really waits for the
+// urgent rows)
+#define SDM_KLAUNCH_MERGED(P, kernel, nwg, W, ...) \
+  do { SDM_KLAUNCH_WAITING(P, 256, kernel, dim3(nwg), dim3(ST), SDM_MERGED_SMEM(W), __VA_ARGS__); emu_sweep_timeout((P)->chol); } while (0)
 static bool solve_refines(CholPlan &C) {
   if (C.refine_mode != 1) return C.refine_mode == 2;
   if (C.noted.host) {
@@ -1339,29 +908,40 @@ static bool solve_refines(CholPlan &C) {
   }
   return C.refine_on;
 }
+// what a sweep settles before its first launch: the growth bound in force, the width, the front table, whether it runs the refinement
+// launches (may_refine: one right-hand side), where its launches leave their notes and its number; marked: the sweep's first diagonal-block
+// launch has told the host that the sweep before it has run
+struct Sweep { double thr; int W; FrontTab tab0; bool refine; int *noted; int seq; bool marked; };
+static Sweep sweep_begin(sdm_plan *P, bool may_refine) {
+  CholPlan &C = P->chol;
+  Sweep sw;
+  sw.thr = C.growth_used; sw.W = C.sbw; sw.tab0 = front_tab(C);
+  sw.refine = may_refine && solve_refines(C);
+  // (inside a graph capture the sweep numbers would be baked into the kernel arguments and replayed stale: a captured sweep leaves
+  // no notes and keeps the mode decided at capture; blocks beyond the bound it was not planned for are substituted, as accurate)
+  sw.noted = C.refine_mode == 1 && !P->capturing ? C.noted.dev() : nullptr;
+  sw.seq = P->capturing ? C.sweep_seq : ++C.sweep_seq;
+  sw.marked = false;
+  return sw;
+}
 // forward sweeps of nrhs right-hand sides side by side (grid.z): rhs + z*rhs_stride -> y + z*y_stride (permuted order);
 // wv = update-vector scratch of wsize doubles per right-hand side
 void solve_fw_batch(sdm_plan *P, const double *rhs, int64_t rhs_stride, double *y, int64_t y_stride, double *wv, int nrhs,
                     double *zdiv, const double *dscale, int l0, int l1, int what) {
   // levels l0 .. l1-1 (l1 < 0: all); what: 1 the assembly launches only (k_sfw_init), 2 everything but them, 3 both
   CholPlan &C = P->chol;
-  const double thr = C.growth_used;
-  const int W = C.sbw;
   FwBatch bt;
   bt.src = nrhs > 1 ? rhs_stride : 0; bt.y = nrhs > 1 ? y_stride : 0; bt.wv = nrhs > 1 ? C.wsize : 0;
-  const FrontTab tab0 = front_tab(C);
+  Sweep sw = sweep_begin(P, nrhs == 1);
+  const double thr = sw.thr;
+  const int W = sw.W, seq = sw.seq;
+  const bool refine = sw.refine;
   if (l1 < 0) l1 = C.nlevels;
-  const bool refine = nrhs == 1 && solve_refines(C);
-  // (inside a graph capture the sweep numbers would be baked into the kernel arguments and replayed stale: a captured sweep leaves
-  // no notes and keeps the mode decided at capture; blocks beyond the bound it was not planned for are substituted, as accurate)
-  int *noted = C.refine_mode == 1 && !P->capturing ? C.noted.dev() : nullptr;
-  const int seq = P->capturing ? C.sweep_seq : ++C.sweep_seq;
-  bool marked = false;
   for (int l = std::max(l0, 0); l < std::min(l1, C.nlevels); l++) {
     const SolveLevel &L = C.slev[l];
     if (L.nfronts == 0) continue;
     const int *list = C.d_levlist.p + C.levptr[l];
-    const FrontTab tab = level_tab(C, tab0, l);
+    const FrontTab tab = level_tab(C, sw.tab0, l);
     const int gather = L.children ? 0 : 1;
     if (!gather && (what & 1)) SDM_KLAUNCH(P, k_sfw_init, dim3(L.nfronts, 1, nrhs), dim3(ST), 0, tab, list, wv, rhs, C.d_perm.p, y, bt);
     if (!(what & 2)) continue;
@@ -1370,36 +950,28 @@ void solve_fw_batch(sdm_plan *P, const double *rhs, int64_t rhs_stride, double *
     const bool may_merge = merge && W > 256 && nrhs == 1 && !refine && tab.one && L.nsb >= 2;
     for (int Pb = 0; Pb < L.nsb; Pb++) {
       const int nbmax = std::min(W, L.maxns - Pb * W);
-      const dim3 gdiag(W <= 256 ? (nbmax + 15) / 16 : tri_grid(nbmax), L.nfronts, nrhs);
-      if (!diag_done) SDM_KLAUNCH(P, k_sfw_diag, gdiag, dim3(ST), SDM_DIAG_SMEM(W), C.fronts.p, C.ST.p, tab, list, wv, rhs,
-                  C.d_perm.p, y, C.sb_g.p, thr, Pb, gather, bt, zdiv, dscale, W, refine ? 1 : 0, C.refine_max, (const double *)nullptr, noted, seq, marked ? -1 : seq - 1, Pb == 0 && may_merge ? C.sweep_cnt.p : (int *)nullptr);
-      marked = true;
+      const dim3 gdiag(diag_grid(nbmax, W), L.nfronts, nrhs);
+      auto diag = [&](int mode, const double *resid, int *note, int mark, int *rearm) {
+        SDM_KLAUNCH(P, k_sfw_diag, gdiag, dim3(ST), SDM_DIAG_SMEM(W), C.fronts.p, C.ST.p, tab, list, wv, rhs, C.d_perm.p, y, C.sb_g.p, thr, Pb, gather, bt,
+                    zdiv, dscale, W, mode, C.refine_max, resid, note, seq, mark, rearm);
+      };
+      if (!diag_done) diag(refine ? 1 : 0, nullptr, sw.noted, sw.marked ? -1 : seq - 1, Pb == 0 && may_merge ? C.sweep_cnt.p : nullptr);
+      sw.marked = true;
       for (int it = 0; refine && it < REFINE_STEPS; it++) {            // (blocks within the bound leave these launches at once)
         SDM_KLAUNCH(P, k_sfw_resid, dim3((nbmax + 63) / 64, L.nfronts), dim3(RT), 0, C.fronts.p, tab, list, wv, rhs, C.d_perm.p, y, C.xfin.p, C.sb_g.p, thr,
                     C.refine_max, Pb, gather, W);
-        SDM_KLAUNCH(P, k_sfw_diag, gdiag, dim3(ST), SDM_DIAG_SMEM(W), C.fronts.p, C.ST.p, tab, list, wv, rhs,
-                    C.d_perm.p, y, C.sb_g.p, thr, Pb, gather, bt, zdiv, dscale, W, 2, C.refine_max, (const double *)C.xfin.p, (int *)nullptr, seq, -1, (int *)nullptr);
+        diag(2, C.xfin.p, nullptr, -1, nullptr);
       }
       const int assign0 = (gather && Pb == 0) ? 1 : 0;
+      const int nrw = row_wgs(L.maxns - (Pb + 1) * W, W);            // the fronts' own rows of later super-blocks
       diag_done = false;
       if (may_merge && L.maxns > (Pb + (merge >= 2 ? 1 : 2)) * W) {
-        const int nrw = W > SEGN ? (L.maxns - (Pb + 1) * W + 1) / 2 : (L.maxns - (Pb + 1) * W + 3) / 4;
-        const int nurg = std::min(nrw, W > SEGN ? W / 2 : W / 4), ndiag = tri_grid(std::min(W, L.maxns - (Pb + 1) * W));
-#ifdef SDM_EMU
-        // (tests/test_emu_concurrent.py: one process per workgroup, the diagonal role really waits for the urgent rows)
-        if (emu_concurrent() && nrw + ndiag <= 256) SDM_KLAUNCH_CONCURRENT(P, k_sfw_rows_diag, dim3(nrw + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.LT.p, C.fronts.p, C.ST.p, tab, list, wv, rhs, C.d_perm.p, y, C.sb_g.p, thr, Pb,
-                    assign0, bt, zdiv, dscale, W, C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nrw - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
-        else
-#endif
-        SDM_KLAUNCH(P, k_sfw_rows_diag, dim3(nrw + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.LT.p, C.fronts.p, C.ST.p, tab, list, wv, rhs, C.d_perm.p, y, C.sb_g.p, thr, Pb,
-                    assign0, bt, zdiv, dscale, W, C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nrw - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
-#ifdef SDM_EMU
-        emu_sweep_timeout(C);
-#endif
+        const int nurg = std::min(nrw, row_wgs(W, W)), ndiag = tri_grid(std::min(W, L.maxns - (Pb + 1) * W));
+        SDM_KLAUNCH_MERGED(P, k_sfw_rows_diag, nrw + ndiag, W, C.LT.p, C.fronts.p, C.ST.p, tab, list, wv, rhs, C.d_perm.p, y, C.sb_g.p, thr, Pb,
+                           assign0, bt, zdiv, dscale, W, C.refine_max, sw.noted, seq, C.sweep_cnt.p, nurg, std::min(nrw - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
         diag_done = true;
-      } else if (L.maxns > (Pb + 1) * W)                             // the fronts' own rows of later super-blocks
-        SDM_KLAUNCH(P, k_sfw_rows, dim3(W > SEGN ? (L.maxns - (Pb + 1) * W + 1) / 2 : (L.maxns - (Pb + 1) * W + 3) / 4, L.nfronts, nrhs), dim3(ST), 0, C.LT.p, tab, list, wv, rhs, C.d_perm.p, y, Pb,
-                    assign0, bt, W);
+      } else if (L.maxns > (Pb + 1) * W)
+        SDM_KLAUNCH(P, k_sfw_rows, dim3(nrw, L.nfronts, nrhs), dim3(ST), 0, C.LT.p, tab, list, wv, rhs, C.d_perm.p, y, Pb, assign0, bt, W);
       if (L.slabs_fw[Pb] > 0)                                        // the rows below the supernodes
         SDM_KLAUNCH(P, k_sfw_step, dim3(L.slabs_fw[Pb], L.nfronts, nrhs), dim3(ST), 0, C.fronts.p, tab, list, wv, y, Pb, assign0, bt, W);
     }
@@ -1411,19 +983,16 @@ void solve_fw_batch(sdm_plan *P, const double *rhs, int64_t rhs_stride, double *
 // was already applied by the forward sweep's final writes)
 static void solve_bw_inplace(sdm_plan *P, double *y, double *yout, const double *dscale, bool skip_plain_init, int l0 = 0, int l1 = -1) {
   CholPlan &C = P->chol;
-  const double thr = C.growth_used;
-  const int W = C.sbw;
-  const FrontTab tab0 = front_tab(C);
+  Sweep sw = sweep_begin(P, true);
+  const double thr = sw.thr;
+  const int W = sw.W, seq = sw.seq;
+  const bool refine = sw.refine;
   if (l1 < 0) l1 = C.nlevels;
-  const bool refine = solve_refines(C);
-  int *noted = C.refine_mode == 1 && !P->capturing ? C.noted.dev() : nullptr;
-  const int seq = P->capturing ? C.sweep_seq : ++C.sweep_seq;
-  bool marked = false;
   for (int l = std::min(l1, C.nlevels) - 1; l >= std::max(l0, 0); l--) {
     const SolveLevel &L = C.slev[l];
     if (L.nfronts == 0) continue;
     const int *list = C.d_levlist.p + C.levptr[l];
-    const FrontTab tab = level_tab(C, tab0, l);
+    const FrontTab tab = level_tab(C, sw.tab0, l);
     if (!(skip_plain_init && !L.below))
       SDM_KLAUNCH(P, k_sbw_init, dim3((L.maxns + SROWS - 1) / SROWS, L.nfronts), dim3(ST), 0, C.fronts.p, tab, list, y, C.xfin.p, dscale);
     bool diag_done = false;
@@ -1431,30 +1000,23 @@ static void solve_bw_inplace(sdm_plan *P, double *y, double *yout, const double 
     const bool may_merge = merge && W > 256 && !refine && tab.one && L.nsb >= 2;
     for (int Q = L.nsb - 1; Q >= 0; Q--) {
       const int nbmax = std::min(W, L.maxns - Q * W);
-      const dim3 gdiag(W <= 256 ? (nbmax + 15) / 16 : tri_grid(nbmax), L.nfronts);
-      if (!diag_done) SDM_KLAUNCH(P, k_sbw_diag, gdiag, dim3(ST), SDM_DIAG_SMEM(W), C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout,
-                  C.d_perm.p, C.sb_g.p, thr, Q, W, refine ? 1 : 0, C.refine_max, (const double *)nullptr, noted, seq, marked ? -1 : seq - 1,
-                  Q == L.nsb - 1 && may_merge ? C.sweep_cnt.p : (int *)nullptr);
-      marked = true;
+      const dim3 gdiag(diag_grid(nbmax, W), L.nfronts);
+      auto diag = [&](int mode, const double *resid, int *note, int mark, int *rearm) {
+        SDM_KLAUNCH(P, k_sbw_diag, gdiag, dim3(ST), SDM_DIAG_SMEM(W), C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout, C.d_perm.p, C.sb_g.p, thr, Q, W,
+                    mode, C.refine_max, resid, note, seq, mark, rearm);
+      };
+      if (!diag_done) diag(refine ? 1 : 0, nullptr, sw.noted, sw.marked ? -1 : seq - 1, Q == L.nsb - 1 && may_merge ? C.sweep_cnt.p : nullptr);
+      sw.marked = true;
       for (int it = 0; refine && it < REFINE_STEPS; it++) {
         SDM_KLAUNCH(P, k_sbw_resid, dim3((nbmax + 3) / 4, L.nfronts), dim3(ST), 0, C.fronts.p, tab, list, y, C.xfin.p, C.wvec.p, C.sb_g.p, thr, C.refine_max, Q, W);
-        SDM_KLAUNCH(P, k_sbw_diag, gdiag, dim3(ST), SDM_DIAG_SMEM(W), C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout,
-                    C.d_perm.p, C.sb_g.p, thr, Q, W, 2, C.refine_max, (const double *)C.wvec.p, (int *)nullptr, seq, -1, (int *)nullptr);
+        diag(2, C.wvec.p, nullptr, -1, nullptr);
       }
       diag_done = false;
-      const int nst = W > SEGN ? Q * (W / 2) : Q * (W / 4);
+      const int nst = Q * row_wgs(W, W);                             // the columns left of super-block Q
       if (may_merge && Q >= (merge >= 2 ? 1 : 2)) {
-        const int nurg = W > SEGN ? W / 2 : W / 4, ndiag = tri_grid(W);
-#ifdef SDM_EMU
-        if (emu_concurrent() && nst + ndiag <= 256) SDM_KLAUNCH_CONCURRENT(P, k_sbw_step_diag, dim3(nst + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout, C.d_perm.p, C.sb_g.p, thr, Q, W,
-                    C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nst - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
-        else
-#endif
-        SDM_KLAUNCH(P, k_sbw_step_diag, dim3(nst + ndiag), dim3(ST), SDM_MERGED_SMEM(W), C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout, C.d_perm.p, C.sb_g.p, thr, Q, W,
-                    C.refine_max, noted, seq, C.sweep_cnt.p, nurg, std::min(nst - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
-#ifdef SDM_EMU
-        emu_sweep_timeout(C);
-#endif
+        const int nurg = row_wgs(W, W), ndiag = tri_grid(W);
+        SDM_KLAUNCH_MERGED(P, k_sbw_step_diag, nst + ndiag, W, C.fronts.p, C.S.p, tab, list, y, C.xfin.p, yout, C.d_perm.p, C.sb_g.p, thr, Q, W,
+                           C.refine_max, sw.noted, seq, C.sweep_cnt.p, nurg, std::min(nst - nurg, sweep_merge_pre()), ndiag, C.sweep_tmo());
         diag_done = true;
       } else if (Q > 0) SDM_KLAUNCH(P, k_sbw_step, dim3(nst, L.nfronts), dim3(ST), 0, C.fronts.p, tab, list, y, C.xfin.p, Q, W);
     }
@@ -1499,12 +1061,3 @@ void solve_run(sdm_plan *P, const double *rhs, double *yout, int mode) {
 }
 
 }  // namespace sdm
-
-#if defined(SDM_PHASES) && !defined(SDM_EMU)
-// tools-only build (python -m sedumi_amd.build --phases): read / reset the in-kernel phase clocks of this file
-extern "C" int sdm_debug_phases_solve(unsigned long long *out32, int reset) {
-  if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(sdm_phase_acc), 32 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  if (reset) { unsigned long long z[32] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(sdm_phase_acc), z, sizeof(z)) != hipSuccess) return 1; }
-  return 0;
-}
-#endif
