@@ -217,6 +217,40 @@ int sdm_bwdpr1(sdm_int m, sdm_int nrhs, sdm_int nden, const sdm_int *dzjc, const
  * perm: 0-based, concatenated per block (sum n_k entries), NULL = identity.  y is the `udsqr` of sdm_getada3. */
 int sdm_invcholfac(const sdm_cone *K, const double *u, const sdm_int *perm, double *y);
 
+/* --- next row: the PSD part of frameit.m / wregion.m ------- */
+
+/* The frame of a PSD block of order n is the unitary factor Qb of qrK (qrK.c:86-227), in one of two forms: */
+#define SDM_FRAME_HOUSEHOLDER 0   /* qrK.c's compact form: lenud + hLen doubles */
+#define SDM_FRAME_EXPLICIT    1   /* Qb itself, n x n per block, Hermitian [Re; Im]: lenud doubles */
+/* SDM_FRAME_HOUSEHOLDER, real block: n x n column major; column k (k < n-1), rows k .. n-1 = the Householder vector c_k (the strict
+ *   upper triangle is not read), column n-1 = beta[0 .. n-2];  Q_k = I - c_k c_k'/beta_k on rows / columns k .. n-1,
+ *   Qb = Q_0 Q_1 ... Q_{n-2}  (qrK.c:86-122; beta_k = 1 with c_k = 0 is the identity, :105-106).
+ * Hermitian block: [Re c (n x n), Im c (n x n), beta (n)];  Q_k = I - c_k c_k^H/beta_k, column n-1 of the two planes is the
+ *   complex sign vector q and Qb = Q_0 ... Q_{n-2} diag(q)  (qrK.c:142-227, reflect.c:232-270, :319-357).
+ * Blocks in K.s order, the first K.rsdpN real.  lenud = sum n_k^2 (2 n_k^2 Hermitian), hLen = sum of the Hermitian n_k. */
+
+/* qb = the explicit Qb of every block (SDM_FRAME_EXPLICIT layout, lenud doubles) from frms in SDM_FRAME_HOUSEHOLDER form:
+ * the expansion sdm_psdframeit / sdm_psdinvjmul run first when they are given a Householder frame. */
+int sdm_psdframe_explicit(const sdm_cone *K, const double *frms, double *qb);
+
+/* x = psdframeit(lab, frms, K)      X_k = Qb_k^H diag(lab_k) Qb_k                                psdframeit.c:65-99
+ * lab: the PSD part of the eigenvalues, rLen + hLen = sum n_k doubles; x: lenud doubles, every block exactly symmetric /
+ * Hermitian (Im diag = 0), as tril2sym / tril2herm leave it.  No PSD blocks: returns 0, launches nothing. */
+int sdm_psdframeit(const sdm_cone *K, const double *lab, const double *frms, int frame_kind, double *x);
+
+/* z = psdinvjmul(xlab, frms, y, K)  Z_k = Qb_k^H ((Qb_k Y_k Qb_k^H) o 2/(x_i + x_j)) Qb_k        psdinvjmul.c:101-157
+ * i.e. X Z + Z X = 2 Y for X = Qb^H diag(xlab) Qb.  Only the lower triangle of every block of y is read (diagonal and below;
+ * reflect.c:52-96), mirrored / conjugated; the division is diagjdiv's (psdinvjmul.c:69-84: y_jj / x_j on the diagonal,
+ * y_ij * (2 / (x_i + x_j)) below it, both planes).  xlab: sum n_k doubles; y, z: lenud doubles, z exactly symmetric /
+ * Hermitian with Im diag = 0. */
+int sdm_psdinvjmul(const sdm_cone *K, const double *xlab, const double *frms, int frame_kind,
+                   const double *y, double *z);
+
+/* LDS bytes a column strip of the frame expansion may take, 0 = default (65536, also the maximum).  A strip is as many columns
+ * of one block as fit (n, or 2 n Hermitian, doubles each), a multiple of 4, 32 at most; a block of which not even 4 columns fit is
+ * expanded in global memory.  Process-wide; for tests, which reach the narrow-strip and the global-memory path at small orders. */
+int sdm_set_frame_lds_budget(sdm_int bytes);
+
 /* ================================================================ tier (2) */
 typedef struct sdm_plan sdm_plan;
 

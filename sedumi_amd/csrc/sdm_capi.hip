@@ -594,6 +594,7 @@ int sdm_plan_kprof_summary(sdm_plan *p, char *buf, sdm_int buflen) {
 struct PlanGuard {
   sdm_plan *p;
   PlanGuard() : p(sdm_plan_create(0, nullptr)) { if (!p) throw std::runtime_error(g_err); }
+  explicit PlanGuard(void *stream) : p(sdm_plan_create(0, stream)) { if (!p) throw std::runtime_error(g_err); }
   ~PlanGuard() { sdm_plan_destroy(p); }
 };
 }  // extern "C"
@@ -857,6 +858,86 @@ int sdm_invcholfac(const sdm_cone *K, const double *u, const sdm_int *perm, doub
   psd_invcholfac(p->stream, du.p, dy.p, perm ? dp.p : nullptr, ns, (int)K->rsdpN, dn, doff, dpo, false);
   SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
   SDM_HIP_CHECK(hipMemcpy(y, dy.p, (size_t)lenud * sizeof(double), hipMemcpyDeviceToHost));
+  SDM_CATCH
+}
+
+// ---- psdframeit / psdinvjmul in qrK's frames (sdm_cone.hip)
+static void frame_args(const sdm_cone *K, int frame_kind, std::vector<int> &ns) {
+  if (!K) throw std::runtime_error("K is null");
+  if (frame_kind != SDM_FRAME_HOUSEHOLDER && frame_kind != SDM_FRAME_EXPLICIT)
+    throw std::runtime_error("frame_kind must be SDM_FRAME_HOUSEHOLDER (0) or SDM_FRAME_EXPLICIT (1)");
+  if (K->sdpN < 0 || K->rsdpN < 0 || K->rsdpN > K->sdpN) throw std::runtime_error("K: 0 <= rsdpN <= length(K.s) expected");
+  sdm_int lenud, plen;
+  cone_blocks(K, ns, lenud, plen);
+  for (int n : ns) if (n < 0) throw std::runtime_error("K.s: negative order");
+}
+// the stream of the calling thread's psdframeit / psdinvjmul calls, created once: a new stream per call costs a new hardware queue, milliseconds
+// against calls of a fraction of one (null where streams have no handles: the plan then makes its own)
+static void *frame_stream() {
+  static thread_local hipStream_t s = nullptr;
+  if (!s && hipStreamCreate(&s) != hipSuccess) s = nullptr;
+  return (void *)s;
+}
+static void h2d(double *d, const double *h, int64_t n) { SDM_HIP_CHECK(hipMemcpy(d, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
+static bool no_psd(const std::vector<int> &ns) { return std::all_of(ns.begin(), ns.end(), [](int n) { return n == 0; }); }
+// the explicit frame on the device (qb): uploaded as it is, or expanded from the Householder form (staged in fr)
+static void frame_upload(sdm_plan *p, const ConeTabs &T, const double *frms, int frame_kind, double *qb, double *fr) {
+  if (frame_kind == SDM_FRAME_EXPLICIT) { h2d(qb, frms, T.lenud); return; }
+  h2d(fr, frms, T.lenfr);
+  cone_expand(p, T, fr, qb);
+}
+int sdm_set_frame_lds_budget(sdm_int bytes) {
+  SDM_TRY
+  cone_set_frame_lds_budget(bytes);
+  SDM_CATCH
+}
+// (every call: one stream, ONE device allocation behind the block tables -- T.data, carved below -- and one synchronise before the read-back)
+int sdm_psdframe_explicit(const sdm_cone *K, const double *frms, double *qb) {
+  SDM_TRY
+  std::vector<int> ns;
+  frame_args(K, SDM_FRAME_HOUSEHOLDER, ns);
+  if (no_psd(ns)) return 0;
+  if (!frms || !qb) throw std::runtime_error("psdframe_explicit: null argument");
+  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
+  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 1, 1, 0);
+  double *dq = T.data, *df = dq + T.lenud;
+  frame_upload(p, T, frms, SDM_FRAME_HOUSEHOLDER, dq, df);
+  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+  SDM_HIP_CHECK(hipMemcpy(qb, dq, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
+  SDM_CATCH
+}
+int sdm_psdframeit(const sdm_cone *K, const double *lab, const double *frms, int frame_kind, double *x) {
+  SDM_TRY
+  std::vector<int> ns;
+  frame_args(K, frame_kind, ns);
+  if (no_psd(ns)) return 0;
+  if (!lab || !frms || !x) throw std::runtime_error("psdframeit: null argument");
+  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
+  const int hh = frame_kind == SDM_FRAME_HOUSEHOLDER ? 1 : 0;
+  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 2, hh, 1);
+  double *dq = T.data, *dx = dq + T.lenud, *dl = dx + T.lenud, *df = dl + T.lenlab;
+  h2d(dl, lab, T.lenlab);
+  frame_upload(p, T, frms, frame_kind, dq, df);
+  cone_frameit(p, T, dq, dl, dx);
+  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+  SDM_HIP_CHECK(hipMemcpy(x, dx, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
+  SDM_CATCH
+}
+int sdm_psdinvjmul(const sdm_cone *K, const double *xlab, const double *frms, int frame_kind, const double *y, double *z) {
+  SDM_TRY
+  std::vector<int> ns;
+  frame_args(K, frame_kind, ns);
+  if (no_psd(ns)) return 0;
+  if (!xlab || !frms || !y || !z) throw std::runtime_error("psdinvjmul: null argument");
+  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
+  const int hh = frame_kind == SDM_FRAME_HOUSEHOLDER ? 1 : 0;
+  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 5, hh, 1);
+  double *dq = T.data, *dy = dq + T.lenud, *t1 = dy + T.lenud, *t2 = t1 + T.lenud, *dz = t2 + T.lenud, *dl = dz + T.lenud, *df = dl + T.lenlab;
+  h2d(dl, xlab, T.lenlab); h2d(dy, y, T.lenud);
+  frame_upload(p, T, frms, frame_kind, dq, df);
+  cone_invjmul(p, T, dq, dl, dy, t1, t2, dz);
+  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+  SDM_HIP_CHECK(hipMemcpy(z, dz, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
   SDM_CATCH
 }
 int sdm_plan_invcholfac(sdm_plan *p, const sdm_int *perm) {

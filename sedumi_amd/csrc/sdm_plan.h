@@ -542,4 +542,20 @@ void ada_datq(sdm_plan *P);     // qpr = values of DAt.q (getDAtm.m:39-44) from 
 // y(perm,perm) = u'u per PSD block (invcholfac.c); u, y device (lenud doubles), perm device int32 0-based or null
 void psd_invcholfac(hipStream_t st, const double *u, double *y, const int *perm, const std::vector<int> &ns, int rsdpN,
                     DevBuf<int> &d_n, DevBuf<int64_t> &d_off, DevBuf<int> &d_poff, bool tables_ready);
+// sdm_cone.hip: psdframeit / psdinvjmul with the explicit frame Qb, and the expansion of qrK's Householder frame into it
+struct ConeTabs {                       // one device allocation: the tables of a list of PSD blocks (orders / offsets, tile lists, the expansion's
+  DevBuf<int64_t> arena;                //   column strips) and behind them the doubles the caller asked for (a host-pointer call: ONE hipMalloc / hipFree)
+  const int *n = nullptr, *herm = nullptr, *loff = nullptr, *items_full = nullptr, *items_low = nullptr, *strips = nullptr;
+  const int64_t *off = nullptr, *foff = nullptr;
+  double *data = nullptr;               // the caller's doubles
+  int nfull = 0, nlow = 0, nstrips = 0;
+  size_t lds = 0;                       // dynamic LDS of the expansion launch
+  int64_t lenud = 0, lenfr = 0, lenlab = 0;   // doubles of x / Qb, of the Householder frames, of lab
+};
+void cone_set_frame_lds_budget(sdm_int bytes);
+// extra doubles behind the tables: n_ud * lenud + n_fr * lenfr + n_lab * lenlab (T.data)
+void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, int n_fr, int n_lab);
+void cone_expand(sdm_plan *P, const ConeTabs &T, const double *frms, double *qb);
+void cone_frameit(sdm_plan *P, const ConeTabs &T, const double *qb, const double *lab, double *x);
+void cone_invjmul(sdm_plan *P, const ConeTabs &T, const double *qb, const double *xlab, const double *y, double *t1, double *t2, double *z);
 }  // namespace sdm

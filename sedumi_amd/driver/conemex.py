@@ -367,14 +367,18 @@ class NativeMex:
     """`.call(name, nlhs, *args)` like a MEX host: the cone algebra above, the hot path and the symbolic analysis through this package's library."""
     error = RuntimeError
 
-    def __init__(self):
+    def __init__(self, device_cone=False):
+        """device_cone: psdframeit / psdinvjmul through the library (sedumi_amd.mex) on the explicit frames this module keeps"""
         from sedumi_amd import mex
         self._mex = mex
+        self.device_cone = bool(device_cone)
         self._native = {"ddot": ddot, "qblkmul": qblkmul, "vecsym": vecsym, "psdframeit": psdframeit, "psdinvjmul": psdinvjmul, "sqrtinv": sqrtinv,
                         "givensrot": givensrot, "partitA": partitA, "extractA": extractA, "findblks": findblks, "sortnnz": sortnnz}
 
     def call(self, name, nlhs, *args):
         args = unwrap_raw(args)
+        if self.device_cone and name in ("psdframeit", "psdinvjmul"):
+            return getattr(self._mex, name)(*args, frame_kind=self._mex.FRAME_EXPLICIT)
         if name in self._native:
             return self._native[name](*args)
         if name == "qrK":

@@ -553,3 +553,76 @@ def invcholfac(u, K, perm=None):
     check(capi.lib().sdm_invcholfac(C.byref(Kc), pf(u), pi(pp) if pp is not None else None, pf(y)))
     del keep
     return y.reshape(-1, 1)
+
+
+# ------------------------------------------------------------- next row
+FRAME_HOUSEHOLDER, FRAME_EXPLICIT = 0, 1        # SDM_FRAME_HOUSEHOLDER, SDM_FRAME_EXPLICIT
+
+
+def _frame_sizes(K, frame_kind):
+    """(Cone struct, keep-alive, lenud, sum(K.s), length of the frame array, lpN, number and total order of the Lorentz cones)"""
+    lpN, q, s, rsdpN = _Kfields(K)
+    lenud = int(np.sum(s[:rsdpN] ** 2) + 2 * np.sum(s[rsdpN:] ** 2))
+    if frame_kind not in (FRAME_HOUSEHOLDER, FRAME_EXPLICIT):
+        raise SdmError("frame_kind must be SDM_FRAME_HOUSEHOLDER (0) or SDM_FRAME_EXPLICIT (1)")
+    lenfr = lenud + (int(np.sum(s[rsdpN:])) if frame_kind == FRAME_HOUSEHOLDER else 0)
+    Kc, keep = capi.make_cone(lpN, q, s, rsdpN)
+    return Kc, keep, lenud, int(np.sum(s)), lenfr, lpN, q.size, int(np.sum(q))
+
+
+def psdframe_explicit(frms, K):
+    """qb = the explicit unitary factor Qb of every PSD block (n x n, Hermitian blocks [Re; Im]; lenud x 1) out of qrK's Householder
+    frames `frms` (lenud + hLen; qrK.c:86-227): Qb = Q_0 ... Q_{n-2} (diag(q) for Hermitian blocks), Q_k = I - c_k c_k^H / beta_k."""
+    Kc, keep, lenud, slen, lenfr, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    frms = f64(frms)
+    if frms.size != lenfr:
+        raise SdmError("frms size mismatch")
+    qb = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_psdframe_explicit(C.byref(Kc), pf(frms), pf(qb)))
+    del keep
+    return qb.reshape(-1, 1)
+
+
+def psdframeit(lab, frms, K, frame_kind=0):
+    """x = psdframeit(lab, frms, K): X = Qb' diag(lab) Qb per PSD block   (psdframeit.c:65-168).
+    lab: sum(K.s) values, or the whole spectral vector (K.l + 2 length(K.q) + sum(K.s), psdframeit.c:134-137); frms: qrK's frames
+    (frame_kind 0, lenud + hLen) or the explicit Qb (frame_kind 1, lenud).  Returns lenud x 1, every block exactly symmetric / Hermitian."""
+    Kc, keep, lenud, slen, lenfr, lpN, nq, _ = _frame_sizes(K, frame_kind)
+    lab, frms = f64(lab), f64(frms)
+    if lab.size != slen:
+        if lab.size != lpN + 2 * nq + slen:
+            raise SdmError("lab size mismatch")
+        lab = np.ascontiguousarray(lab[lpN + 2 * nq:])
+    if frms.size != lenfr:
+        raise SdmError("frms size mismatch")
+    x = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_psdframeit(C.byref(Kc), pf(lab), pf(frms), C.c_int(frame_kind), pf(x)))
+    del keep
+    return x.reshape(-1, 1)
+
+
+def psdinvjmul(xlab, frms, y, K, frame_kind=0):
+    """z = psdinvjmul(xlab, frms, y, K): X Z + Z X = 2 Y for X = Qb' diag(xlab) Qb, per PSD block   (psdinvjmul.c:101-227).
+    xlab as `lab` of psdframeit; y: lenud values or a whole cone vector (K.l + sum(K.q) + lenud, psdinvjmul.c:195-198), of which only the
+    lower triangle of every block is read.  Returns lenud x 1, every block exactly symmetric / Hermitian."""
+    Kc, keep, lenud, slen, lenfr, lpN, nq, qdim = _frame_sizes(K, frame_kind)
+    xlab, frms, y = f64(xlab), f64(frms), f64(y)
+    if y.size != lenud:
+        if y.size != lpN + qdim + lenud:
+            raise SdmError("size y mismatch")
+        y = np.ascontiguousarray(y[lpN + qdim:])
+    if xlab.size != slen:
+        if xlab.size != lpN + 2 * nq + slen:
+            raise SdmError("size xlab mismatch")
+        xlab = np.ascontiguousarray(xlab[lpN + 2 * nq:])
+    if frms.size != lenfr:
+        raise SdmError("size xfrm mismatch")
+    z = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_psdinvjmul(C.byref(Kc), pf(xlab), pf(frms), C.c_int(frame_kind), pf(y), pf(z)))
+    del keep
+    return z.reshape(-1, 1)
+
+
+def set_frame_lds_budget(nbytes):
+    """LDS bytes per column strip of the frame expansion (sdm_set_frame_lds_budget), 0 = default."""
+    check(capi.lib().sdm_set_frame_lds_budget(C.c_int64(int(nbytes))))
