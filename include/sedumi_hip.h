@@ -251,6 +251,26 @@ int sdm_psdinvjmul(const sdm_cone *K, const double *xlab, const double *frms, in
  * expanded in global memory.  Process-wide; for tests, which reach the narrow-strip and the global-memory path at small orders. */
 int sdm_set_frame_lds_budget(sdm_int bytes);
 
+/* --- next row: the producer of the frame --------------------- */
+
+/* [q, r] = qrK(x, K)   qrK.c:86-296.  x: lenud doubles (the PSD part only, as the gateway requires).  Per block x = Qb R.
+ * frame_kind SDM_FRAME_HOUSEHOLDER: q = lenud + hLen doubles in qrK.c's compact form (above), in the reference's conventions:
+ *   real       d_k = SIGN(x_kk) ||x(k:,k)|| with SIGN(0) = +1, c_kk = x_kk + d_k, beta_k = d_k c_kk (1 when that is 0), R_kk = -d_k:
+ *              the diagonal of R is not made non-negative;
+ *   Hermitian  u_kk = -(x_kk/|x_kk|) ||x_k|| (-||x_k|| when x_kk = 0), c_kk = x_kk - u_kk, beta_k = ||x_k|| (||x_k|| + |x_kk|) (1 when
+ *              ||x_k|| = 0), then the sign column q_i = u_ii/|u_ii|, R_ii = |u_ii|, Im R_ii = 0, row i of R right of the diagonal times conj(q_i);
+ *   every entry of q outside c, beta and the sign column is 0.0.
+ * SDM_FRAME_EXPLICIT: q = Qb itself (lenud doubles), expanded on the device before the read-back.
+ * r: lenud doubles, triu = R.  The reference leaves the strict lower triangle undefined; here it is 0.  NULL = not wanted (not copied back).
+ * A blocked right-looking Householder QR: panels of 32 columns, the trailing matrix updated with the panel's compact-WY form on the FP64
+ * matrix cores; a block's bits depend on nothing but the block.  No PSD blocks: returns 0, launches nothing. */
+int sdm_qrk(const sdm_cone *K, const double *x, int frame_kind, double *q, double *r);
+
+/* LDS bytes the panel of a block may take in sdm_qrk's panel step, 0 = default (40960, also the maximum).  A panel (rows j0 .. n-1 of 32
+ * columns, both planes of a Hermitian block) that does not fit is factored in place in global memory, with the same bits.
+ * Process-wide; for tests, which reach the global-memory residence at small orders. */
+int sdm_set_qr_panel_lds_budget(sdm_int bytes);
+
 /* ================================================================ tier (2) */
 typedef struct sdm_plan sdm_plan;
 

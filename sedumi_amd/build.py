@@ -74,7 +74,8 @@ MEXHOST_LIB = os.path.join(LIBDIR, "libsdm_mexhost.so")
 SHIM_DIR = os.path.join(HERE, "mexshims")
 MEX_OUT = os.path.join(LIBDIR, "mex")
 SHIMS = ["getada", "getada1", "getada2", "getada3", "blkchol", "fwblkslv", "bwblkslv", "ordmmdmex", "symfctmex", "choltmpsiz", "cholsplit",
-         "symbfwblk", "finsymbden", "dpr1fact", "fwdpr1", "bwdpr1", "invcholfac", "incorder", "adendotd", "adenscale", "psdframeit", "psdinvjmul"]
+         "symbfwblk", "finsymbden", "dpr1fact", "fwdpr1", "bwdpr1", "invcholfac", "incorder", "adendotd", "adenscale", "psdframeit", "psdinvjmul",
+         "qrK"]
 
 
 def _newer(target, deps):

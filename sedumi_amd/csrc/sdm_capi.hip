@@ -940,6 +940,32 @@ int sdm_psdinvjmul(const sdm_cone *K, const double *xlab, const double *frms, in
   SDM_HIP_CHECK(hipMemcpy(z, dz, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
   SDM_CATCH
 }
+// ---- qrK, the producer of those frames (sdm_qrk.hip); the call shape of the N5 entry points above
+int sdm_set_qr_panel_lds_budget(sdm_int bytes) {
+  SDM_TRY
+  qrk_set_panel_lds_budget(bytes);
+  SDM_CATCH
+}
+int sdm_qrk(const sdm_cone *K, const double *x, int frame_kind, double *q, double *r) {
+  SDM_TRY
+  std::vector<int> ns;
+  frame_args(K, frame_kind, ns);
+  if (no_psd(ns)) return 0;
+  if (!x || !q) throw std::runtime_error("qrk: null argument");
+  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
+  QrkSteps S; qrk_plan(S, ns, (int)K->rsdpN);
+  const int ex = frame_kind == SDM_FRAME_EXPLICIT ? 1 : 0;
+  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 1 + ex, 1, 0, S.words());
+  double *dr = T.data, *dqb = dr + T.lenud, *dq = dr + (1 + ex) * T.lenud, *area = dq + T.lenfr;
+  h2d(dr, x, T.lenud);
+  qrk_run(p, T, S, area, dq, dr);
+  if (ex) cone_expand(p, T, dq, dqb);
+  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+  if (ex) SDM_HIP_CHECK(hipMemcpy(q, dqb, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
+  else SDM_HIP_CHECK(hipMemcpy(q, dq, (size_t)T.lenfr * sizeof(double), hipMemcpyDeviceToHost));
+  if (r) SDM_HIP_CHECK(hipMemcpy(r, dr, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
+  SDM_CATCH
+}
 int sdm_plan_invcholfac(sdm_plan *p, const sdm_int *perm) {
   SDM_TRY
   AdaPlan &A = p->ada;

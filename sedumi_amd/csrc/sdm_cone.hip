@@ -257,7 +257,7 @@ void cone_set_frame_lds_budget(sdm_int bytes) {
 }
 
 // block tables, tile lists and the strips of the expansion for the PSD blocks `ns` (the first rsdpN real, the others Hermitian)
-void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, int n_fr, int n_lab) {
+void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, int n_fr, int n_lab, int64_t extra) {
   const int nb = (int)ns.size();
   std::vector<int> bn(std::max(nb, 1), 0), bh(std::max(nb, 1), 0), bl(std::max(nb, 1), 0), full, low;
   std::vector<int64_t> bo(std::max(nb, 1), 0), bf(std::max(nb, 1), 0);
@@ -304,7 +304,7 @@ void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, i
   const size_t w_int = img.size(), w_dat = w_int + ints.size() / 2;
   img.resize(w_dat);
   memcpy(img.data() + w_int, ints.data(), ints.size() * sizeof(int));
-  T.arena.alloc(w_dat + (size_t)(n_ud * o + n_fr * fo + n_lab * lo));
+  T.arena.alloc(w_dat + (size_t)(n_ud * o + n_fr * fo + n_lab * lo + extra));
   SDM_HIP_CHECK(hipMemcpy(T.arena.p, img.data(), w_dat * sizeof(int64_t), hipMemcpyHostToDevice));
   T.off = T.arena.p; T.foff = T.arena.p + bo.size();
   const int *ip = (const int *)(T.arena.p + w_int);

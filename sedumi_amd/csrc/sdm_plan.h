@@ -554,8 +554,23 @@ struct ConeTabs {                       // one device allocation: the tables of 
 };
 void cone_set_frame_lds_budget(sdm_int bytes);
 // extra doubles behind the tables: n_ud * lenud + n_fr * lenfr + n_lab * lenlab (T.data)
-void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, int n_fr, int n_lab);
+// (+ `extra` more doubles behind those)
+void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, int n_fr, int n_lab, int64_t extra = 0);
 void cone_expand(sdm_plan *P, const ConeTabs &T, const double *frms, double *qb);
 void cone_frameit(sdm_plan *P, const ConeTabs &T, const double *qb, const double *lab, double *x);
 void cone_invjmul(sdm_plan *P, const ConeTabs &T, const double *qb, const double *xlab, const double *y, double *t1, double *t2, double *z);
+// sdm_qrk.hip: [q, r] = qrK(x, K) as a blocked Householder QR with compact-WY trailing updates
+struct QrkSteps {                       // host side of one call: the launches of every panel step and the image of their item tables
+  struct Step { int j0, panel0, npanel, strip0, nstrip, tile0, ntile; size_t lds; };
+  std::vector<Step> steps;              // panel [j0, j0 + QR_NB) of every block that reaches it; *0 = first item, n* = items (grid size)
+  int sign0 = 0, nsign = 0;             // the Hermitian blocks' sign-column pass
+  std::vector<int64_t> img;             // [workspace offset per block | int32 items, 4 per item]
+  size_t w_items = 0;                   // 8-byte words of img before the items
+  int64_t ws = 0;                       // doubles of workspace (T and W per block)
+  int64_t words() const { return ws + (int64_t)img.size(); }   // doubles qrk_run needs in `area`
+};
+void qrk_set_panel_lds_budget(sdm_int bytes);
+void qrk_plan(QrkSteps &S, const std::vector<int> &ns, int rsdpN);
+// q (lenfr doubles, device) and r (lenud doubles, device, holding x on entry) of every block of T; area: S.words() doubles on the device
+void qrk_run(sdm_plan *P, const ConeTabs &T, const QrkSteps &S, double *area, double *q, double *r);
 }  // namespace sdm

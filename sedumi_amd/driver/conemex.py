@@ -14,7 +14,10 @@ Where a reference routine hands an OPAQUE array from one MEX to another, the arr
 the reference's compact forms:
 
   * the "frame" of a PSD block (qrK's first output, consumed by psdframeit / psdinvjmul): the unitary factor Qb of  x = Qb R  stored EXPLICITLY (n x n,
-    Hermitian blocks as [Re; Im]) -- the reference stores n - 1 Householder vectors and their betas (qrK.c:76-120);
+    Hermitian blocks as [Re; Im]) -- the reference stores n - 1 Householder vectors and their betas (qrK.c:76-120).  With
+    NativeMex(device_qr=True) the library's qrK (sedumi_amd.mex.qrK) makes that array on the device, still the explicit Qb; R
+    then follows the reference's sign convention (qrK.c:96-108: on real blocks R_kk = -sign(x_kk) ||x_k||, so the diagonal may be negative;
+    on Hermitian blocks it is real and non-negative);
   * the rotations of urotorder (its outputs gjc, g, consumed by givensrot): the unitary G of the re-pivoting stored explicitly (gjc = block offsets
     into g) -- the reference stores Givens pairs (urotorder.c:79-180).  The re-pivoting itself is LAPACK's QR with column pivoting whenever the
     reference's stability test (urotorder.c:110-122: max |u(k, later columns)|^2 > maxu^2 * d_k) fails, the identity otherwise.
@@ -367,11 +370,13 @@ class NativeMex:
     """`.call(name, nlhs, *args)` like a MEX host: the cone algebra above, the hot path and the symbolic analysis through this package's library."""
     error = RuntimeError
 
-    def __init__(self, device_cone=False):
-        """device_cone: psdframeit / psdinvjmul through the library (sedumi_amd.mex) on the explicit frames this module keeps"""
+    def __init__(self, device_cone=False, device_qr=False):
+        """device_cone: psdframeit / psdinvjmul through the library (sedumi_amd.mex, SURVEY 8f N5) on the explicit frames this module keeps;
+        device_qr: qrK through the library too (N6), handing out the same explicit frames"""
         from sedumi_amd import mex
         self._mex = mex
         self.device_cone = bool(device_cone)
+        self.device_qr = bool(device_qr)
         self._native = {"ddot": ddot, "qblkmul": qblkmul, "vecsym": vecsym, "psdframeit": psdframeit, "psdinvjmul": psdinvjmul, "sqrtinv": sqrtinv,
                         "givensrot": givensrot, "partitA": partitA, "extractA": extractA, "findblks": findblks, "sortnnz": sortnnz}
 
@@ -379,6 +384,8 @@ class NativeMex:
         args = unwrap_raw(args)
         if self.device_cone and name in ("psdframeit", "psdinvjmul"):
             return getattr(self._mex, name)(*args, frame_kind=self._mex.FRAME_EXPLICIT)
+        if self.device_qr and name == "qrK":
+            return self._mex.qrK(*args, nlhs=nlhs, frame_kind=self._mex.FRAME_EXPLICIT)
         if name in self._native:
             return self._native[name](*args)
         if name == "qrK":

@@ -626,3 +626,24 @@ def psdinvjmul(xlab, frms, y, K, frame_kind=0):
 def set_frame_lds_budget(nbytes):
     """LDS bytes per column strip of the frame expansion (sdm_set_frame_lds_budget), 0 = default."""
     check(capi.lib().sdm_set_frame_lds_budget(C.c_int64(int(nbytes))))
+
+
+# ------------------------------------------------------------- next row (SURVEY 8f N6)
+def qrK(x, K, nlhs=1, frame_kind=FRAME_HOUSEHOLDER):
+    """[q, r] = qrK(x, K): x = Qb R per PSD block in the reference's conventions (qrK.c:86-296; include/sedumi_hip.h at sdm_qrk).
+    x: lenud values, the PSD part only.  q: qrK's compact Householder frames (frame_kind 0, lenud + hLen) or the explicit Qb (frame_kind 1,
+    lenud); r: lenud x 1, triu = R (real blocks: the diagonal may be negative), strict lower triangle 0; only fetched with nlhs > 1."""
+    Kc, keep, lenud, slen, lenfr, _, _, _ = _frame_sizes(K, frame_kind)
+    x = f64(x)
+    if x.size != lenud:
+        raise SdmError("size mismatch x")
+    q = np.zeros(lenfr, dtype=np.float64)
+    r = np.zeros(lenud, dtype=np.float64) if nlhs > 1 else None
+    check(capi.lib().sdm_qrk(C.byref(Kc), pf(x), C.c_int(frame_kind), pf(q), pf(r) if r is not None else None))
+    del keep
+    return (q.reshape(-1, 1), r.reshape(-1, 1)) if nlhs > 1 else q.reshape(-1, 1)
+
+
+def set_qr_panel_lds_budget(nbytes):
+    """LDS bytes the panel of a block may take in qrK's panel step (sdm_set_qr_panel_lds_budget), 0 = default."""
+    check(capi.lib().sdm_set_qr_panel_lds_budget(C.c_int64(int(nbytes))))
