@@ -1,9 +1,9 @@
-// sdm_capi.hip -- extern "C" entry points of libsedumi_hip.so (include/sedumi_hip.h).
+// sdm_capi.hip -- extern "C" entry points of libsedumi_hip.so (include/sedumi_hip.h): the error state, the device calls and the plan tier
+// (sdm_plan_*).  The stateless MEX equivalents are in sdm_gateways.hip, the cached ones in sdm_mexcache.hip.
 #include "../../include/sedumi_hip.h"
 #include "sdm_plan.h"
 #include <algorithm>
 #include <cstring>
-#include <memory>
 
 namespace sdm {
 static thread_local std::string g_err;
@@ -32,13 +32,6 @@ static void require_begun(sdm_plan *p, const char *fn) {
   if (!p->has_chol) throw std::runtime_error(std::string(fn) + ": no symbolic factor set");
   if (!p->chol.begun) throw std::runtime_error(std::string(fn) + ": no factorisation begun (sdm_plan_blkchol_begin)");
 }
-
-#define SDM_TRY try {
-#define SDM_CATCH                                              \
-  }                                                            \
-  catch (const std::exception &e) { set_error(e.what()); return 1; } \
-  catch (...) { set_error("unknown error"); return 1; }        \
-  return 0;
 
 extern "C" {
 
@@ -237,18 +230,20 @@ int sdm_plan_copy(sdm_plan *p, const char *name, void *devptr, sdm_int offset, s
   check_plan_health(p);
   SDM_CATCH
 }
-int sdm_plan_blkchol(sdm_plan *p, const sdm_cholpars *pars, int use_absd) {
+// the whole factorisation, or (begin) its first step of three: sdm_plan_blkchol_begin / _levels / _end
+static int plan_factor(sdm_plan *p, const sdm_cholpars *pars, int use_absd, bool begin) {
   SDM_TRY
-  if (!p->has_chol) throw std::runtime_error("sdm_plan_blkchol: no symbolic factor set");
+  if (!p->has_chol) throw std::runtime_error(std::string(begin ? "sdm_plan_blkchol_begin" : "sdm_plan_blkchol") + ": no symbolic factor set");
   const sdm_cholpars q = chol_pars(pars);
   p->dense.factored = false;                        // the dense-column factors belong to the previous L, d
-  chol_factor(p, q.canceltol, q.maxu, q.abstol, use_absd);
+  (begin ? chol_begin : chol_factor)(p, q.canceltol, q.maxu, q.abstol, use_absd);
   SDM_CATCH
 }
+int sdm_plan_blkchol(sdm_plan *p, const sdm_cholpars *pars, int use_absd) { return plan_factor(p, pars, use_absd, false); }
 int sdm_plan_blkchol_wait(sdm_plan *p, const sdm_cholpars *pars, int use_absd) {
   SDM_TRY
   for (int attempt = 0; ; attempt++) {
-    if (sdm_plan_blkchol(p, pars, use_absd)) throw std::runtime_error(g_err);
+    plan_ok(sdm_plan_blkchol(p, pars, use_absd));
     SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
     // (a factor time-out switches the plan to the launch-per-panel path; one of a merged sweep before it only switches merging off)
     if (!(chol_wait_timeouts(p) & TMO_FACTOR)) break;
@@ -279,14 +274,7 @@ int sdm_plan_front_layout(sdm_plan *p, sdm_int *nlevels, sdm_int *level, sdm_int
   }
   SDM_CATCH
 }
-int sdm_plan_blkchol_begin(sdm_plan *p, const sdm_cholpars *pars, int use_absd) {
-  SDM_TRY
-  if (!p->has_chol) throw std::runtime_error("sdm_plan_blkchol_begin: no symbolic factor set");
-  const sdm_cholpars q = chol_pars(pars);
-  p->dense.factored = false;
-  chol_begin(p, q.canceltol, q.maxu, q.abstol, use_absd);
-  SDM_CATCH
-}
+int sdm_plan_blkchol_begin(sdm_plan *p, const sdm_cholpars *pars, int use_absd) { return plan_factor(p, pars, use_absd, true); }
 // ---- one dense front factored block-column-cyclically by several ranks (include/sedumi_hip.h: "One front across GPUs")
 int sdm_plan_blkchol_panels(sdm_plan *p, sdm_int l0, sdm_int l1, sdm_int pan0, sdm_int pan1, int world, int rank, int blk) {
   SDM_TRY
@@ -358,24 +346,15 @@ int sdm_plan_pivots(sdm_plan *p, sdm_int *nskip, sdm_int *skip_idx, double *skip
   if (nadd) *nadd = na;
   SDM_CATCH
 }
-int sdm_plan_fwsolve(sdm_plan *p) {
+static int plan_solve(sdm_plan *p, int mode, const char *fn) {          // mode bits: 1 fw | 2 ./d | 4 bw (solve_run)
   SDM_TRY
-  if (!p->factored) throw std::runtime_error("fwsolve: no factor resident");
-  solve_run(p, p->rhs.p, p->y.p, 1);
+  if (!p->factored) throw std::runtime_error(std::string(fn) + ": no factor resident");
+  solve_run(p, p->rhs.p, p->y.p, mode);
   SDM_CATCH
 }
-int sdm_plan_bwsolve(sdm_plan *p) {
-  SDM_TRY
-  if (!p->factored) throw std::runtime_error("bwsolve: no factor resident");
-  solve_run(p, p->rhs.p, p->y.p, 4);
-  SDM_CATCH
-}
-int sdm_plan_ldlsolve(sdm_plan *p) {
-  SDM_TRY
-  if (!p->factored) throw std::runtime_error("ldlsolve: no factor resident");
-  solve_run(p, p->rhs.p, p->y.p, 7);
-  SDM_CATCH
-}
+int sdm_plan_fwsolve(sdm_plan *p) { return plan_solve(p, 1, "fwsolve"); }
+int sdm_plan_bwsolve(sdm_plan *p) { return plan_solve(p, 4, "bwsolve"); }
+int sdm_plan_ldlsolve(sdm_plan *p) { return plan_solve(p, 7, "ldlsolve"); }
 int sdm_plan_set_growth_max(sdm_plan *p, double growth_max) {
   SDM_TRY
   if (!(growth_max >= 0.0)) throw std::runtime_error("growth_max must be >= 0");
@@ -467,6 +446,30 @@ int sdm_plan_wrappcg(sdm_plan *p, const sdm_cgpars *cg, double y0, int use_rb, i
   SDM_HIP_CHECK(hipSetDevice(p->device));
   pcg_wrap(p, cg, y0, use_rb != 0, use_perm != 0, k, info);
   check_plan_health(p);
+  SDM_CATCH
+}
+// y(perm,perm) = u'u of every PSD block of the plan (invcholfac.c): from the resident "u" into "udsqr"
+int sdm_plan_invcholfac(sdm_plan *p, const sdm_int *perm) {
+  SDM_TRY
+  AdaPlan &A = p->ada;
+  if (A.lenud == 0) return 0;
+  if (A.ufac.n < (size_t)A.lenud) throw std::runtime_error("invcholfac: upload buffer \"u\" first");
+  std::vector<int> ns(A.psd_n.begin(), A.psd_n.end()), p32;
+  if (perm) {
+    // the permutation is staged in a plan-owned pinned buffer that outlives the call (the copy is asynchronous);
+    // inside a graph capture the copy node would keep reading that buffer at every replay, so a NEW permutation
+    // cannot be handed over there -- upload it before the capture
+    if (p->capturing) throw std::runtime_error("sdm_plan_invcholfac: a permutation cannot be uploaded inside a graph capture (the captured copy would replay from the staging buffer)");
+    perm32(perm, ns, p32);
+    if (A.ic_perm.n < p32.size()) A.ic_perm.alloc(p32.size());
+    A.ic_perm_host.ensure(p32.size());
+    SDM_HIP_CHECK(hipStreamSynchronize(p->stream));                 // an earlier copy out of the staging buffer may be pending
+    memcpy(A.ic_perm_host.p, p32.data(), p32.size() * sizeof(int));
+    SDM_HIP_CHECK(hipMemcpyAsync(A.ic_perm.p, A.ic_perm_host.p, p32.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    A.ic_has_perm = true;
+  }
+  const bool ready = A.ic_n.n == ns.size() && !ns.empty();           // block tables: once per plan (set_ada resets them)
+  psd_invcholfac(p->stream, A.ufac.p, A.udsqr.p, perm ? A.ic_perm.p : nullptr, ns, (int)A.rsdpN, A.ic_n, A.ic_off, A.ic_poff, ready);
   SDM_CATCH
 }
 // ---- resident dense-column unit (deninfac.m:58-94)
@@ -590,403 +593,4 @@ int sdm_plan_kprof_summary(sdm_plan *p, char *buf, sdm_int buflen) {
   SDM_CATCH
 }
 
-// ------------------------------------------------- tier (1): MEX equivalents
-struct PlanGuard {
-  sdm_plan *p;
-  PlanGuard() : p(sdm_plan_create(0, nullptr)) { if (!p) throw std::runtime_error(g_err); }
-  explicit PlanGuard(void *stream) : p(sdm_plan_create(0, stream)) { if (!p) throw std::runtime_error(g_err); }
-  ~PlanGuard() { sdm_plan_destroy(p); }
-};
-}  // extern "C"
-
-namespace sdm {
-void gw_upload_invperm(DevBuf<int> &buf, const sdm_int *perm, sdm_int m) {
-  std::vector<int> ip(m);
-  for (sdm_int k = 0; k < m; k++) {
-    if (perm[k] < 0 || perm[k] >= m) throw std::runtime_error("permutation entry out of range");
-    ip[perm[k]] = (int)k;
-  }
-  buf.upload(ip);
-}
-// a trivial symbolic factor (diagonal) so that an ADA-only plan can be built
-static void set_trivial_chol(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir) {
-  std::vector<sdm_int> Ljc(m + 1), Lir(m), perm(m), xs(m + 1);
-  for (sdm_int j = 0; j <= m; j++) { Ljc[j] = j; xs[j] = j; }
-  for (sdm_int j = 0; j < m; j++) { Lir[j] = j; perm[j] = j; }
-  if (sdm_plan_set_chol(p, m, Ljc.data(), Lir.data(), perm.data(), m, xs.data(), ADAjc, ADAir)) throw std::runtime_error(g_err);
-}
-// ---- gateway-shaped plans: a plan that holds exactly what ONE of the getada gateways needs (its slice of At / DAt.q, the ADA
-// pattern).  The stateless tier-1 entry points below build one per call; the MEX cache (sdm_mexcache.hip) keeps them.
-// ADA' values live in p->ada_val, absd in p->absd.
-void gw_build_getada1(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, const sdm_int *Ajc, const sdm_int *Air,
-                      const double *Apr, const sdm_int *Ajc2, sdm_int lpN, sdm_int lorN, const sdm_int *qblkstart) {
-  set_trivial_chol(p, m, ADAjc, ADAir);
-  // only the LP/Lorentz rows matter here: present At as if it had no PSD part (rows >= qblkstart[lorN] are never touched:
-  // Ajc2 is the end of the LP/Lorentz nonzeros)
-  std::vector<sdm_int> Qjc(m + 1, 0);
-  const sdm_int nlq = lorN > 0 ? qblkstart[lorN] : lpN;
-  ada_build(p, nlq, m, Ajc, Air, Apr, Ajc2, lpN, lorN, 0, 0, nullptr, qblkstart, nullptr, Qjc.data(), nullptr, ADAjc, ADAir);
-}
-void gw_run_getada1(sdm_plan *p, const int *d_invperm, const double *dl, const double *ddet) {
-  AdaPlan &A = p->ada;
-  if (A.lpN) SDM_HIP_CHECK(hipMemcpyAsync(A.dl.p, dl, A.lpN * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  if (A.lorN) SDM_HIP_CHECK(hipMemcpyAsync(A.ddet.p, ddet, A.lorN * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  SDM_HIP_CHECK(hipMemsetAsync(p->ada_val.p, 0, p->ada_val.n * sizeof(double), p->stream));   // getada1.c:222-225
-  if (A.nnz_lq == 0) return;     // no LP / Lorentz nonzeros at all (MAXCUT): ADA' stays zero -- nnz(ADA') empty sparse dots took 0.6 ms at n = 4000
-  ada_lq(p, p->ada_val.p, d_invperm, false);
-}
-bool gw_getada1_is_zero(sdm_plan *p) { return p->ada.nnz_lq == 0; }
-void gw_build_getada2(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int lorN, const sdm_int *Qjc, const sdm_int *Qir) {
-  set_trivial_chol(p, m, ADAjc, ADAir);
-  std::vector<sdm_int> Ajc(m + 1, 0), qb(lorN + 1, 0);
-  ada_build(p, lorN, m, Ajc.data(), nullptr, nullptr, Ajc.data(), 0, lorN, 0, 0, nullptr, qb.data(), nullptr, Qjc, Qir, ADAjc, ADAir);
-}
-void gw_run_getada2(sdm_plan *p, const int *d_invperm, const double *Qpr) {   // p->ada_val in/out
-  if (p->ada.nnzQ) SDM_HIP_CHECK(hipMemcpyAsync(p->ada.qpr.p, Qpr, p->ada.nnzQ * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  ada_q(p, p->ada_val.p, d_invperm, true);
-}
-void gw_build_getada3(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int N, const sdm_int *Ajc, const sdm_int *Air,
-                      const double *Apr, const sdm_int *Ajc1, const sdm_cone *K, const sdm_int *psd_blkstart) {
-  set_trivial_chol(p, m, ADAjc, ADAir);
-  std::vector<sdm_int> Qjc(m + 1, 0), qb(K->lorN + 1, 0);
-  // the LP/Lorentz rows are not read by getada3: describe them as plain LP rows up to the first PSD row
-  const sdm_int nlq = K->sdpN > 0 ? psd_blkstart[0] : N;
-  ada_build(p, N, m, Ajc, Air, Apr, Ajc1, nlq, 0, K->sdpN, K->rsdpN, K->sdpNL, qb.data(), psd_blkstart, Qjc.data(), nullptr, ADAjc, ADAir);
-}
-void gw_run_getada3(sdm_plan *p, const double *udsqr, bool input_is_zero) {   // p->ada_val in/out, p->absd out
-  // input_is_zero: the ADA' handed in is known to be the zero matrix (getada1 / getada2 had nothing to add): nothing to symmetrise
-  // (k_symmetrize + the copy back: 0.28 ms and 1.8 GB of traffic at n = 4000)
-  if (p->ada.lenud) SDM_HIP_CHECK(hipMemcpyAsync(p->ada.udsqr.p, udsqr, p->ada.lenud * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  ada_psd(p, p->ada_val.p, nullptr, !input_is_zero);
-}
-// the whole ADA' of a problem WITHOUT PSD blocks (getada.m:13-40)
-void gw_build_getada(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, const sdm_int *Ajc, const sdm_int *Air, const double *Apr,
-                     sdm_int lpN, sdm_int lorN, const sdm_int *qblkstart, const sdm_int *Qjc, const sdm_int *Qir) {
-  set_trivial_chol(p, m, ADAjc, ADAir);
-  const sdm_int nlq = lorN > 0 ? qblkstart[lorN] : lpN;             // = K.mainblks(3)-1: rows of Alq (getada.m:25)
-  std::vector<sdm_int> ajc2(m), zq(m + 1, 0);
-  for (sdm_int j = 0; j < m; j++) ajc2[j] = std::lower_bound(Air + Ajc[j], Air + Ajc[j + 1], nlq) - Air;
-  ada_build(p, nlq, m, Ajc, Air, Apr, ajc2.data(), lpN, lorN, 0, 0, nullptr, qblkstart, nullptr,
-            lorN > 0 ? Qjc : zq.data(), lorN > 0 ? Qir : nullptr, ADAjc, ADAir);
-}
-void gw_run_getada(sdm_plan *p, const double *dl, const double *ddet, const double *Qpr) {
-  AdaPlan &A = p->ada;
-  if (A.lpN) SDM_HIP_CHECK(hipMemcpyAsync(A.dl.p, dl, A.lpN * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  if (A.lorN) SDM_HIP_CHECK(hipMemcpyAsync(A.ddet.p, ddet, A.lorN * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  if (A.lorN && A.nnzQ) SDM_HIP_CHECK(hipMemcpyAsync(A.qpr.p, Qpr, A.nnzQ * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  if (sdm_plan_getada(p)) throw std::runtime_error(g_err);
-}
-// values of ADA' (and absd) back to the host once the plan's stream has drained
-void gw_download(sdm_plan *p, double *ADApr, double *absd) {
-  if (ADApr) SDM_HIP_CHECK(hipMemcpyAsync(ADApr, p->ada_val.p, p->ada_val.n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-  if (absd) SDM_HIP_CHECK(hipMemcpyAsync(absd, p->absd.p, (size_t)p->chol.m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-}
-}  // namespace sdm
-
-extern "C" {
-
-int sdm_getada1(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int N, const sdm_int *Ajc,
-                const sdm_int *Air, const double *Apr, const sdm_int *Ajc2, const sdm_int *perm, sdm_int lpN,
-                const double *dl, sdm_int lorN, const double *ddet, const sdm_int *qblkstart, double *ADApr) {
-  SDM_TRY
-  (void)N;
-  PlanGuard G; sdm_plan *p = G.p;
-  gw_build_getada1(p, m, ADAjc, ADAir, Ajc, Air, Apr, Ajc2, lpN, lorN, qblkstart);
-  DevBuf<int> ip; gw_upload_invperm(ip, perm, m);
-  gw_run_getada1(p, ip.p, dl, ddet);
-  gw_download(p, ADApr, nullptr);
-  SDM_CATCH
-}
-
-int sdm_getada2(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, double *ADApr, sdm_int lorN,
-                const sdm_int *Qjc, const sdm_int *Qir, const double *Qpr, const sdm_int *qperm) {
-  SDM_TRY
-  if (lorN <= 0) return 0;                          // getada2.c:154-155: nothing to do without Lorentz cones
-  PlanGuard G; sdm_plan *p = G.p;
-  gw_build_getada2(p, m, ADAjc, ADAir, lorN, Qjc, Qir);
-  SDM_HIP_CHECK(hipMemcpy(p->ada_val.p, ADApr, (size_t)ADAjc[m] * sizeof(double), hipMemcpyHostToDevice));
-  DevBuf<int> ip; gw_upload_invperm(ip, qperm, m);
-  gw_run_getada2(p, ip.p, Qpr);
-  gw_download(p, ADApr, nullptr);
-  SDM_CATCH
-}
-
-int sdm_getada3(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, double *ADApr, sdm_int N, const sdm_int *Ajc,
-                const sdm_int *Air, const double *Apr, const sdm_int *Ajc1, const sdm_int *sperm, const double *udsqr,
-                const sdm_cone *K, const sdm_int *psd_blkstart, double *absd) {
-  SDM_TRY
-  (void)sperm;   // the sum is independent of the fill order (see sdm_ada.hip header)
-  PlanGuard G; sdm_plan *p = G.p;
-  gw_build_getada3(p, m, ADAjc, ADAir, N, Ajc, Air, Apr, Ajc1, K, psd_blkstart);
-  SDM_HIP_CHECK(hipMemcpy(p->ada_val.p, ADApr, (size_t)ADAjc[m] * sizeof(double), hipMemcpyHostToDevice));
-  gw_run_getada3(p, udsqr, false);
-  gw_download(p, ADApr, absd);
-  SDM_CATCH
-}
-
-// absd = getada(A, K, d, DAt) with the global ADA_sedumi_ : the whole ADA' of a problem WITHOUT PSD blocks
-// (sedumi.m:446-448 -> getada.m:13-40):  ADA = DAt.q' DAt.q + Alq' diag([d.l; -d.det; d.det per norm-bound row]) Alq
-// on the pattern of the global (both triangles), absd = diag(ADA) (getada.m:40).
-int sdm_getada(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int N, const sdm_int *Ajc, const sdm_int *Air,
-               const double *Apr, sdm_int lpN, const double *dl, sdm_int lorN, const double *ddet, const sdm_int *qblkstart,
-               const sdm_int *Qjc, const sdm_int *Qir, const double *Qpr, double *ADApr, double *absd) {
-  SDM_TRY
-  (void)N;
-  PlanGuard G; sdm_plan *p = G.p;
-  gw_build_getada(p, m, ADAjc, ADAir, Ajc, Air, Apr, lpN, lorN, qblkstart, Qjc, Qir);
-  gw_run_getada(p, dl, ddet, Qpr);
-  gw_download(p, ADApr, absd);
-  SDM_CATCH
-}
-
-int sdm_blkchol(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const sdm_int *perm, sdm_int nsuper,
-                const sdm_int *xsuper, const sdm_int *Xjc, const sdm_int *Xir, const double *Xpr,
-                const sdm_cholpars *pars, const double *absd, double *Lpr, double *d, sdm_int *nskip,
-                sdm_int *skip_idx, double *skip_val, sdm_int *nadd, sdm_int *add_idx, double *add_val) {
-  SDM_TRY
-  PlanGuard G; sdm_plan *p = G.p;
-  if (sdm_plan_set_chol(p, m, Ljc, Lir, perm, nsuper, xsuper, Xjc, Xir)) throw std::runtime_error(g_err);
-  SDM_HIP_CHECK(hipMemcpy(p->ada_val.p, Xpr, (size_t)Xjc[m] * sizeof(double), hipMemcpyHostToDevice));
-  if (absd) SDM_HIP_CHECK(hipMemcpy(p->absd.p, absd, m * sizeof(double), hipMemcpyHostToDevice));
-  if (sdm_plan_blkchol_wait(p, pars, absd ? 1 : 0)) throw std::runtime_error(g_err);
-  if (sdm_plan_download(p, "lpr", Lpr, Ljc[m])) throw std::runtime_error(g_err);
-  if (sdm_plan_download(p, "d", d, m)) throw std::runtime_error(g_err);
-  if (sdm_plan_pivots(p, nskip, skip_idx, skip_val, nadd, add_idx, add_val)) throw std::runtime_error(g_err);
-  SDM_CATCH
-}
-
-static void solve_common(bool fw, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr,
-                         const sdm_int *perm, sdm_int nsuper, const sdm_int *xsuper, sdm_int nrhs, const double *b,
-                         double *y) {
-  PlanGuard G; sdm_plan *p = G.p;
-  // the ADA pattern is irrelevant for a solve: use an empty one
-  std::vector<sdm_int> zj(m + 1, 0), idperm;
-  if (!perm) { idperm.resize(m); for (sdm_int i = 0; i < m; i++) idperm[i] = i; perm = idperm.data(); }
-  if (sdm_plan_set_chol(p, m, Ljc, Lir, perm, nsuper, xsuper, zj.data(), nullptr)) throw std::runtime_error(g_err);
-  chol_load_factor(p, Lpr);
-  for (sdm_int c = 0; c < nrhs; c++) {
-    SDM_HIP_CHECK(hipMemcpyAsync(p->rhs.p, b + c * m, m * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    if ((fw ? sdm_plan_fwsolve(p) : sdm_plan_bwsolve(p))) throw std::runtime_error(g_err);
-    SDM_HIP_CHECK(hipMemcpyAsync(y + c * m, p->y.p, m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-  }
-}
-int sdm_fwblkslv(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, const sdm_int *perm,
-                 sdm_int nsuper, const sdm_int *xsuper, sdm_int nrhs, const double *b, double *y) {
-  SDM_TRY
-  solve_common(true, m, Ljc, Lir, Lpr, perm, nsuper, xsuper, nrhs, b, y);
-  SDM_CATCH
-}
-int sdm_bwblkslv(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, const sdm_int *perm,
-                 sdm_int nsuper, const sdm_int *xsuper, sdm_int nrhs, const double *b, double *y) {
-  SDM_TRY
-  solve_common(false, m, Ljc, Lir, Lpr, perm, nsuper, xsuper, nrhs, b, y);
-  SDM_CATCH
-}
-
-// sparse right-hand sides: the pattern (Yjc,Yir) from symbfwblk is closed under the solve, so the
-// dense solve restricted to it gives exactly the entries selfwsolve / selbwsolve define.
-static void solve_sparse(bool fw, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr,
-                         const sdm_int *perm, sdm_int nsuper, const sdm_int *xsuper, sdm_int n, const sdm_int *Bjc,
-                         const sdm_int *Bir, const double *Bpr, const sdm_int *Yjc, const sdm_int *Yir, double *Ypr) {
-  PlanGuard G; sdm_plan *p = G.p;
-  std::vector<sdm_int> zj(m + 1, 0), idperm(m);
-  for (sdm_int i = 0; i < m; i++) idperm[i] = i;
-  // forward variant maps b through invperm == dense fwblkslv on a dense copy of b (fwblkslv.c:308-309);
-  // backward variant uses no permutation at all (bwblkslv.c:279-291)
-  if (sdm_plan_set_chol(p, m, Ljc, Lir, fw ? perm : idperm.data(), nsuper, xsuper, zj.data(), nullptr)) throw std::runtime_error(g_err);
-  chol_load_factor(p, Lpr);
-  std::vector<double> col(m), out(m);
-  for (sdm_int c = 0; c < n; c++) {
-    std::fill(col.begin(), col.end(), 0.0);
-    for (sdm_int t = Bjc[c]; t < Bjc[c + 1]; t++) col[Bir[t]] = Bpr[t];
-    SDM_HIP_CHECK(hipMemcpyAsync(p->rhs.p, col.data(), m * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    if ((fw ? sdm_plan_fwsolve(p) : sdm_plan_bwsolve(p))) throw std::runtime_error(g_err);
-    SDM_HIP_CHECK(hipMemcpyAsync(out.data(), p->y.p, m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-    for (sdm_int t = Yjc[c]; t < Yjc[c + 1]; t++) Ypr[t] = out[Yir[t]];
-  }
-}
-int sdm_fwblkslv_sparse(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, const sdm_int *perm,
-                        sdm_int nsuper, const sdm_int *xsuper, sdm_int n, const sdm_int *Bjc, const sdm_int *Bir,
-                        const double *Bpr, const sdm_int *Yjc, const sdm_int *Yir, double *Ypr) {
-  SDM_TRY
-  solve_sparse(true, m, Ljc, Lir, Lpr, perm, nsuper, xsuper, n, Bjc, Bir, Bpr, Yjc, Yir, Ypr);
-  SDM_CATCH
-}
-int sdm_bwblkslv_sparse(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, sdm_int nsuper,
-                        const sdm_int *xsuper, sdm_int n, const sdm_int *Bjc, const sdm_int *Bir, const double *Bpr,
-                        const sdm_int *Yjc, const sdm_int *Yir, double *Ypr) {
-  SDM_TRY
-  solve_sparse(false, m, Ljc, Lir, Lpr, nullptr, nsuper, xsuper, n, Bjc, Bir, Bpr, Yjc, Yir, Ypr);
-  SDM_CATCH
-}
-
-
-// ---- invcholfac
-static void cone_blocks(const sdm_cone *K, std::vector<int> &ns, sdm_int &lenud, sdm_int &plen) {
-  ns.resize((size_t)K->sdpN); lenud = 0; plen = 0;
-  for (sdm_int k = 0; k < K->sdpN; k++) {
-    ns[k] = (int)K->sdpNL[k];
-    lenud += (k < K->rsdpN ? 1 : 2) * K->sdpNL[k] * K->sdpNL[k];
-    plen += K->sdpNL[k];
-  }
-}
-static void perm32(const sdm_int *perm, const std::vector<int> &ns, std::vector<int> &out) {
-  out.clear();
-  size_t o = 0;
-  for (int n : ns) {
-    std::vector<char> seen((size_t)n, 0);
-    for (int i = 0; i < n; i++) {
-      const sdm_int v = perm[o + i];
-      if (v < 0 || v >= n || seen[(size_t)v]) throw std::runtime_error("perm is not a permutation of the block");
-      seen[(size_t)v] = 1; out.push_back((int)v);
-    }
-    o += (size_t)n;
-  }
-}
-int sdm_invcholfac(const sdm_cone *K, const double *u, const sdm_int *perm, double *y) {
-  SDM_TRY
-  std::vector<int> ns, p32; sdm_int lenud, plen;
-  cone_blocks(K, ns, lenud, plen);
-  if (lenud == 0) return 0;
-  PlanGuard G; sdm_plan *p = G.p;
-  DevBuf<double> du, dy; DevBuf<int> dp, dn, dpo; DevBuf<int64_t> doff;
-  du.upload(u, (size_t)lenud); dy.alloc((size_t)lenud);
-  if (perm) { perm32(perm, ns, p32); dp.upload(p32); }
-  psd_invcholfac(p->stream, du.p, dy.p, perm ? dp.p : nullptr, ns, (int)K->rsdpN, dn, doff, dpo, false);
-  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-  SDM_HIP_CHECK(hipMemcpy(y, dy.p, (size_t)lenud * sizeof(double), hipMemcpyDeviceToHost));
-  SDM_CATCH
-}
-
-// ---- psdframeit / psdinvjmul in qrK's frames (sdm_cone.hip)
-static void frame_args(const sdm_cone *K, int frame_kind, std::vector<int> &ns) {
-  if (!K) throw std::runtime_error("K is null");
-  if (frame_kind != SDM_FRAME_HOUSEHOLDER && frame_kind != SDM_FRAME_EXPLICIT)
-    throw std::runtime_error("frame_kind must be SDM_FRAME_HOUSEHOLDER (0) or SDM_FRAME_EXPLICIT (1)");
-  if (K->sdpN < 0 || K->rsdpN < 0 || K->rsdpN > K->sdpN) throw std::runtime_error("K: 0 <= rsdpN <= length(K.s) expected");
-  sdm_int lenud, plen;
-  cone_blocks(K, ns, lenud, plen);
-  for (int n : ns) if (n < 0) throw std::runtime_error("K.s: negative order");
-}
-// the stream of the calling thread's psdframeit / psdinvjmul calls, created once: a new stream per call costs a new hardware queue, milliseconds
-// against calls of a fraction of one (null where streams have no handles: the plan then makes its own)
-static void *frame_stream() {
-  static thread_local hipStream_t s = nullptr;
-  if (!s && hipStreamCreate(&s) != hipSuccess) s = nullptr;
-  return (void *)s;
-}
-static void h2d(double *d, const double *h, int64_t n) { SDM_HIP_CHECK(hipMemcpy(d, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
-static bool no_psd(const std::vector<int> &ns) { return std::all_of(ns.begin(), ns.end(), [](int n) { return n == 0; }); }
-// the explicit frame on the device (qb): uploaded as it is, or expanded from the Householder form (staged in fr)
-static void frame_upload(sdm_plan *p, const ConeTabs &T, const double *frms, int frame_kind, double *qb, double *fr) {
-  if (frame_kind == SDM_FRAME_EXPLICIT) { h2d(qb, frms, T.lenud); return; }
-  h2d(fr, frms, T.lenfr);
-  cone_expand(p, T, fr, qb);
-}
-int sdm_set_frame_lds_budget(sdm_int bytes) {
-  SDM_TRY
-  cone_set_frame_lds_budget(bytes);
-  SDM_CATCH
-}
-// (every call: one stream, ONE device allocation behind the block tables -- T.data, carved below -- and one synchronise before the read-back)
-int sdm_psdframe_explicit(const sdm_cone *K, const double *frms, double *qb) {
-  SDM_TRY
-  std::vector<int> ns;
-  frame_args(K, SDM_FRAME_HOUSEHOLDER, ns);
-  if (no_psd(ns)) return 0;
-  if (!frms || !qb) throw std::runtime_error("psdframe_explicit: null argument");
-  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
-  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 1, 1, 0);
-  double *dq = T.data, *df = dq + T.lenud;
-  frame_upload(p, T, frms, SDM_FRAME_HOUSEHOLDER, dq, df);
-  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-  SDM_HIP_CHECK(hipMemcpy(qb, dq, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
-  SDM_CATCH
-}
-int sdm_psdframeit(const sdm_cone *K, const double *lab, const double *frms, int frame_kind, double *x) {
-  SDM_TRY
-  std::vector<int> ns;
-  frame_args(K, frame_kind, ns);
-  if (no_psd(ns)) return 0;
-  if (!lab || !frms || !x) throw std::runtime_error("psdframeit: null argument");
-  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
-  const int hh = frame_kind == SDM_FRAME_HOUSEHOLDER ? 1 : 0;
-  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 2, hh, 1);
-  double *dq = T.data, *dx = dq + T.lenud, *dl = dx + T.lenud, *df = dl + T.lenlab;
-  h2d(dl, lab, T.lenlab);
-  frame_upload(p, T, frms, frame_kind, dq, df);
-  cone_frameit(p, T, dq, dl, dx);
-  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-  SDM_HIP_CHECK(hipMemcpy(x, dx, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
-  SDM_CATCH
-}
-int sdm_psdinvjmul(const sdm_cone *K, const double *xlab, const double *frms, int frame_kind, const double *y, double *z) {
-  SDM_TRY
-  std::vector<int> ns;
-  frame_args(K, frame_kind, ns);
-  if (no_psd(ns)) return 0;
-  if (!xlab || !frms || !y || !z) throw std::runtime_error("psdinvjmul: null argument");
-  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
-  const int hh = frame_kind == SDM_FRAME_HOUSEHOLDER ? 1 : 0;
-  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 5, hh, 1);
-  double *dq = T.data, *dy = dq + T.lenud, *t1 = dy + T.lenud, *t2 = t1 + T.lenud, *dz = t2 + T.lenud, *dl = dz + T.lenud, *df = dl + T.lenlab;
-  h2d(dl, xlab, T.lenlab); h2d(dy, y, T.lenud);
-  frame_upload(p, T, frms, frame_kind, dq, df);
-  cone_invjmul(p, T, dq, dl, dy, t1, t2, dz);
-  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-  SDM_HIP_CHECK(hipMemcpy(z, dz, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
-  SDM_CATCH
-}
-// ---- qrK, the producer of those frames (sdm_qrk.hip); the call shape of the N5 entry points above
-int sdm_set_qr_panel_lds_budget(sdm_int bytes) {
-  SDM_TRY
-  qrk_set_panel_lds_budget(bytes);
-  SDM_CATCH
-}
-int sdm_qrk(const sdm_cone *K, const double *x, int frame_kind, double *q, double *r) {
-  SDM_TRY
-  std::vector<int> ns;
-  frame_args(K, frame_kind, ns);
-  if (no_psd(ns)) return 0;
-  if (!x || !q) throw std::runtime_error("qrk: null argument");
-  PlanGuard G(frame_stream()); sdm_plan *p = G.p;
-  QrkSteps S; qrk_plan(S, ns, (int)K->rsdpN);
-  const int ex = frame_kind == SDM_FRAME_EXPLICIT ? 1 : 0;
-  ConeTabs T; cone_tables(T, ns, (int)K->rsdpN, 1 + ex, 1, 0, S.words());
-  double *dr = T.data, *dqb = dr + T.lenud, *dq = dr + (1 + ex) * T.lenud, *area = dq + T.lenfr;
-  h2d(dr, x, T.lenud);
-  qrk_run(p, T, S, area, dq, dr);
-  if (ex) cone_expand(p, T, dq, dqb);
-  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-  if (ex) SDM_HIP_CHECK(hipMemcpy(q, dqb, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
-  else SDM_HIP_CHECK(hipMemcpy(q, dq, (size_t)T.lenfr * sizeof(double), hipMemcpyDeviceToHost));
-  if (r) SDM_HIP_CHECK(hipMemcpy(r, dr, (size_t)T.lenud * sizeof(double), hipMemcpyDeviceToHost));
-  SDM_CATCH
-}
-int sdm_plan_invcholfac(sdm_plan *p, const sdm_int *perm) {
-  SDM_TRY
-  AdaPlan &A = p->ada;
-  if (A.lenud == 0) return 0;
-  if (A.ufac.n < (size_t)A.lenud) throw std::runtime_error("invcholfac: upload buffer \"u\" first");
-  std::vector<int> ns(A.psd_n.begin(), A.psd_n.end()), p32;
-  if (perm) {
-    // the permutation is staged in a plan-owned pinned buffer that outlives the call (the copy is asynchronous);
-    // inside a graph capture the copy node would keep reading that buffer at every replay, so a NEW permutation
-    // cannot be handed over there -- upload it before the capture
-    if (p->capturing) throw std::runtime_error("sdm_plan_invcholfac: a permutation cannot be uploaded inside a graph capture (the captured copy would replay from the staging buffer)");
-    perm32(perm, ns, p32);
-    if (A.ic_perm.n < p32.size()) A.ic_perm.alloc(p32.size());
-    A.ic_perm_host.ensure(p32.size());
-    SDM_HIP_CHECK(hipStreamSynchronize(p->stream));                 // an earlier copy out of the staging buffer may be pending
-    memcpy(A.ic_perm_host.p, p32.data(), p32.size() * sizeof(int));
-    SDM_HIP_CHECK(hipMemcpyAsync(A.ic_perm.p, A.ic_perm_host.p, p32.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
-    A.ic_has_perm = true;
-  }
-  const bool ready = A.ic_n.n == ns.size() && !ns.empty();           // block tables: once per plan (set_ada resets them)
-  psd_invcholfac(p->stream, A.ufac.p, A.udsqr.p, perm ? A.ic_perm.p : nullptr, ns, (int)A.rsdpN, A.ic_n, A.ic_off, A.ic_poff, ready);
-  SDM_CATCH
-}
 }  // extern "C"

@@ -220,12 +220,6 @@ void pr1_solve(bool backward, sdm_int m, sdm_int nrhs, sdm_int nden, const sdm_i
 }  // namespace sdm
 
 using namespace sdm;
-#define SDM_TRY try {
-#define SDM_CATCH                                                    \
-  }                                                                  \
-  catch (const std::exception &e) { set_error(e.what()); return 1; } \
-  catch (...) { set_error("unknown error"); return 1; }              \
-  return 0;
 
 extern "C" {
 

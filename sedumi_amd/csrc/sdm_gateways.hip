@@ -1,0 +1,376 @@
+// sdm_gateways.hip -- extern "C" entry points of libsedumi_hip.so (include/sedumi_hip.h), tier (1): the stateless MEX equivalents.  Each
+// builds a plan (sdm_capi.hip) for the one call; the gw_* plan builders are shared with the cache behind the mexFunction shims
+// (sdm_mexcache.hip).
+#include "../../include/sedumi_hip.h"
+#include "sdm_plan.h"
+#include <algorithm>
+#include <cstring>
+
+using namespace sdm;
+
+struct PlanGuard {                                     // the plan of one stateless call
+  sdm_plan *p;
+  explicit PlanGuard(void *stream = nullptr) : p(sdm_plan_create(0, stream)) { if (!p) plan_ok(1); }
+  ~PlanGuard() { sdm_plan_destroy(p); }
+};
+
+namespace sdm {
+void gw_upload_invperm(DevBuf<int> &buf, const sdm_int *perm, sdm_int m) {
+  std::vector<int> ip(m);
+  for (sdm_int k = 0; k < m; k++) {
+    if (perm[k] < 0 || perm[k] >= m) throw std::runtime_error("permutation entry out of range");
+    ip[perm[k]] = (int)k;
+  }
+  buf.upload(ip);
+}
+// a trivial symbolic factor (diagonal) so that an ADA-only plan can be built
+static void set_trivial_chol(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir) {
+  std::vector<sdm_int> Ljc(m + 1), Lir(m), perm(m), xs(m + 1);
+  for (sdm_int j = 0; j <= m; j++) { Ljc[j] = j; xs[j] = j; }
+  for (sdm_int j = 0; j < m; j++) { Lir[j] = j; perm[j] = j; }
+  plan_ok(sdm_plan_set_chol(p, m, Ljc.data(), Lir.data(), perm.data(), m, xs.data(), ADAjc, ADAir));
+}
+// ---- gateway-shaped plans: a plan that holds exactly what ONE of the getada gateways needs (its slice of At / DAt.q, the ADA
+// pattern).  The stateless tier-1 entry points below build one per call; the MEX cache (sdm_mexcache.hip) keeps them.
+// ADA' values live in p->ada_val, absd in p->absd.
+void gw_build_getada1(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, const sdm_int *Ajc, const sdm_int *Air,
+                      const double *Apr, const sdm_int *Ajc2, sdm_int lpN, sdm_int lorN, const sdm_int *qblkstart) {
+  set_trivial_chol(p, m, ADAjc, ADAir);
+  // only the LP/Lorentz rows matter here: present At as if it had no PSD part (rows >= qblkstart[lorN] are never touched:
+  // Ajc2 is the end of the LP/Lorentz nonzeros)
+  std::vector<sdm_int> Qjc(m + 1, 0);
+  const sdm_int nlq = lorN > 0 ? qblkstart[lorN] : lpN;
+  ada_build(p, nlq, m, Ajc, Air, Apr, Ajc2, lpN, lorN, 0, 0, nullptr, qblkstart, nullptr, Qjc.data(), nullptr, ADAjc, ADAir);
+}
+void gw_run_getada1(sdm_plan *p, const int *d_invperm, const double *dl, const double *ddet) {
+  AdaPlan &A = p->ada;
+  if (A.lpN) SDM_HIP_CHECK(hipMemcpyAsync(A.dl.p, dl, A.lpN * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  if (A.lorN) SDM_HIP_CHECK(hipMemcpyAsync(A.ddet.p, ddet, A.lorN * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  SDM_HIP_CHECK(hipMemsetAsync(p->ada_val.p, 0, p->ada_val.n * sizeof(double), p->stream));   // getada1.c:222-225
+  if (A.nnz_lq == 0) return;     // no LP / Lorentz nonzeros at all (MAXCUT): ADA' stays zero -- nnz(ADA') empty sparse dots took 0.6 ms at n = 4000
+  ada_lq(p, p->ada_val.p, d_invperm, false);
+}
+bool gw_getada1_is_zero(sdm_plan *p) { return p->ada.nnz_lq == 0; }
+void gw_build_getada2(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int lorN, const sdm_int *Qjc, const sdm_int *Qir) {
+  set_trivial_chol(p, m, ADAjc, ADAir);
+  std::vector<sdm_int> Ajc(m + 1, 0), qb(lorN + 1, 0);
+  ada_build(p, lorN, m, Ajc.data(), nullptr, nullptr, Ajc.data(), 0, lorN, 0, 0, nullptr, qb.data(), nullptr, Qjc, Qir, ADAjc, ADAir);
+}
+void gw_run_getada2(sdm_plan *p, const int *d_invperm, const double *Qpr) {   // p->ada_val in/out
+  if (p->ada.nnzQ) SDM_HIP_CHECK(hipMemcpyAsync(p->ada.qpr.p, Qpr, p->ada.nnzQ * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  ada_q(p, p->ada_val.p, d_invperm, true);
+}
+void gw_build_getada3(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int N, const sdm_int *Ajc, const sdm_int *Air,
+                      const double *Apr, const sdm_int *Ajc1, const sdm_cone *K, const sdm_int *psd_blkstart) {
+  set_trivial_chol(p, m, ADAjc, ADAir);
+  std::vector<sdm_int> Qjc(m + 1, 0), qb(K->lorN + 1, 0);
+  // the LP/Lorentz rows are not read by getada3: describe them as plain LP rows up to the first PSD row
+  const sdm_int nlq = K->sdpN > 0 ? psd_blkstart[0] : N;
+  ada_build(p, N, m, Ajc, Air, Apr, Ajc1, nlq, 0, K->sdpN, K->rsdpN, K->sdpNL, qb.data(), psd_blkstart, Qjc.data(), nullptr, ADAjc, ADAir);
+}
+void gw_run_getada3(sdm_plan *p, const double *udsqr, bool input_is_zero) {   // p->ada_val in/out, p->absd out
+  // input_is_zero: the ADA' handed in is known to be the zero matrix (getada1 / getada2 had nothing to add): nothing to symmetrise
+  // (k_symmetrize + the copy back: 0.28 ms and 1.8 GB of traffic at n = 4000)
+  if (p->ada.lenud) SDM_HIP_CHECK(hipMemcpyAsync(p->ada.udsqr.p, udsqr, p->ada.lenud * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  ada_psd(p, p->ada_val.p, nullptr, !input_is_zero);
+}
+// the whole ADA' of a problem WITHOUT PSD blocks (getada.m:13-40)
+void gw_build_getada(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, const sdm_int *Ajc, const sdm_int *Air, const double *Apr,
+                     sdm_int lpN, sdm_int lorN, const sdm_int *qblkstart, const sdm_int *Qjc, const sdm_int *Qir) {
+  set_trivial_chol(p, m, ADAjc, ADAir);
+  const sdm_int nlq = lorN > 0 ? qblkstart[lorN] : lpN;             // = K.mainblks(3)-1: rows of Alq (getada.m:25)
+  std::vector<sdm_int> ajc2(m), zq(m + 1, 0);
+  for (sdm_int j = 0; j < m; j++) ajc2[j] = std::lower_bound(Air + Ajc[j], Air + Ajc[j + 1], nlq) - Air;
+  ada_build(p, nlq, m, Ajc, Air, Apr, ajc2.data(), lpN, lorN, 0, 0, nullptr, qblkstart, nullptr,
+            lorN > 0 ? Qjc : zq.data(), lorN > 0 ? Qir : nullptr, ADAjc, ADAir);
+}
+void gw_run_getada(sdm_plan *p, const double *dl, const double *ddet, const double *Qpr) {
+  AdaPlan &A = p->ada;
+  if (A.lpN) SDM_HIP_CHECK(hipMemcpyAsync(A.dl.p, dl, A.lpN * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  if (A.lorN) SDM_HIP_CHECK(hipMemcpyAsync(A.ddet.p, ddet, A.lorN * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  if (A.lorN && A.nnzQ) SDM_HIP_CHECK(hipMemcpyAsync(A.qpr.p, Qpr, A.nnzQ * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  plan_ok(sdm_plan_getada(p));
+}
+// values of ADA' (and absd) back to the host once the plan's stream has drained
+void gw_download(sdm_plan *p, double *ADApr, double *absd) {
+  if (ADApr) SDM_HIP_CHECK(hipMemcpyAsync(ADApr, p->ada_val.p, p->ada_val.n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  if (absd) SDM_HIP_CHECK(hipMemcpyAsync(absd, p->absd.p, (size_t)p->chol.m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+}
+// the PSD blocks of K and a permutation of each (invcholfac, here and on a plan; the frame calls)
+void cone_blocks(const sdm_cone *K, std::vector<int> &ns, sdm_int &lenud, sdm_int &plen) {
+  ns.resize((size_t)K->sdpN); lenud = 0; plen = 0;
+  for (sdm_int k = 0; k < K->sdpN; k++) {
+    ns[k] = (int)K->sdpNL[k];
+    lenud += (k < K->rsdpN ? 1 : 2) * K->sdpNL[k] * K->sdpNL[k];
+    plen += K->sdpNL[k];
+  }
+}
+void perm32(const sdm_int *perm, const std::vector<int> &ns, std::vector<int> &out) {
+  out.clear();
+  size_t o = 0;
+  for (int n : ns) {
+    std::vector<char> seen((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+      const sdm_int v = perm[o + i];
+      if (v < 0 || v >= n || seen[(size_t)v]) throw std::runtime_error("perm is not a permutation of the block");
+      seen[(size_t)v] = 1; out.push_back((int)v);
+    }
+    o += (size_t)n;
+  }
+}
+}  // namespace sdm
+
+extern "C" {
+
+int sdm_getada1(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int N, const sdm_int *Ajc,
+                const sdm_int *Air, const double *Apr, const sdm_int *Ajc2, const sdm_int *perm, sdm_int lpN,
+                const double *dl, sdm_int lorN, const double *ddet, const sdm_int *qblkstart, double *ADApr) {
+  SDM_TRY
+  (void)N;
+  PlanGuard G; sdm_plan *p = G.p;
+  gw_build_getada1(p, m, ADAjc, ADAir, Ajc, Air, Apr, Ajc2, lpN, lorN, qblkstart);
+  DevBuf<int> ip; gw_upload_invperm(ip, perm, m);
+  gw_run_getada1(p, ip.p, dl, ddet);
+  gw_download(p, ADApr, nullptr);
+  SDM_CATCH
+}
+
+int sdm_getada2(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, double *ADApr, sdm_int lorN,
+                const sdm_int *Qjc, const sdm_int *Qir, const double *Qpr, const sdm_int *qperm) {
+  SDM_TRY
+  if (lorN <= 0) return 0;                          // getada2.c:154-155: nothing to do without Lorentz cones
+  PlanGuard G; sdm_plan *p = G.p;
+  gw_build_getada2(p, m, ADAjc, ADAir, lorN, Qjc, Qir);
+  SDM_HIP_CHECK(hipMemcpy(p->ada_val.p, ADApr, (size_t)ADAjc[m] * sizeof(double), hipMemcpyHostToDevice));
+  DevBuf<int> ip; gw_upload_invperm(ip, qperm, m);
+  gw_run_getada2(p, ip.p, Qpr);
+  gw_download(p, ADApr, nullptr);
+  SDM_CATCH
+}
+
+int sdm_getada3(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, double *ADApr, sdm_int N, const sdm_int *Ajc,
+                const sdm_int *Air, const double *Apr, const sdm_int *Ajc1, const sdm_int *sperm, const double *udsqr,
+                const sdm_cone *K, const sdm_int *psd_blkstart, double *absd) {
+  SDM_TRY
+  (void)sperm;   // the sum is independent of the fill order (see sdm_ada.hip header)
+  PlanGuard G; sdm_plan *p = G.p;
+  gw_build_getada3(p, m, ADAjc, ADAir, N, Ajc, Air, Apr, Ajc1, K, psd_blkstart);
+  SDM_HIP_CHECK(hipMemcpy(p->ada_val.p, ADApr, (size_t)ADAjc[m] * sizeof(double), hipMemcpyHostToDevice));
+  gw_run_getada3(p, udsqr, false);
+  gw_download(p, ADApr, absd);
+  SDM_CATCH
+}
+
+// absd = getada(A, K, d, DAt) with the global ADA_sedumi_ : the whole ADA' of a problem WITHOUT PSD blocks
+// (sedumi.m:446-448 -> getada.m:13-40):  ADA = DAt.q' DAt.q + Alq' diag([d.l; -d.det; d.det per norm-bound row]) Alq
+// on the pattern of the global (both triangles), absd = diag(ADA) (getada.m:40).
+int sdm_getada(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int N, const sdm_int *Ajc, const sdm_int *Air,
+               const double *Apr, sdm_int lpN, const double *dl, sdm_int lorN, const double *ddet, const sdm_int *qblkstart,
+               const sdm_int *Qjc, const sdm_int *Qir, const double *Qpr, double *ADApr, double *absd) {
+  SDM_TRY
+  (void)N;
+  PlanGuard G; sdm_plan *p = G.p;
+  gw_build_getada(p, m, ADAjc, ADAir, Ajc, Air, Apr, lpN, lorN, qblkstart, Qjc, Qir);
+  gw_run_getada(p, dl, ddet, Qpr);
+  gw_download(p, ADApr, absd);
+  SDM_CATCH
+}
+
+int sdm_blkchol(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const sdm_int *perm, sdm_int nsuper,
+                const sdm_int *xsuper, const sdm_int *Xjc, const sdm_int *Xir, const double *Xpr,
+                const sdm_cholpars *pars, const double *absd, double *Lpr, double *d, sdm_int *nskip,
+                sdm_int *skip_idx, double *skip_val, sdm_int *nadd, sdm_int *add_idx, double *add_val) {
+  SDM_TRY
+  PlanGuard G; sdm_plan *p = G.p;
+  plan_ok(sdm_plan_set_chol(p, m, Ljc, Lir, perm, nsuper, xsuper, Xjc, Xir));
+  SDM_HIP_CHECK(hipMemcpy(p->ada_val.p, Xpr, (size_t)Xjc[m] * sizeof(double), hipMemcpyHostToDevice));
+  if (absd) SDM_HIP_CHECK(hipMemcpy(p->absd.p, absd, m * sizeof(double), hipMemcpyHostToDevice));
+  plan_ok(sdm_plan_blkchol_wait(p, pars, absd ? 1 : 0));
+  plan_ok(sdm_plan_download(p, "lpr", Lpr, Ljc[m]));
+  plan_ok(sdm_plan_download(p, "d", d, m));
+  plan_ok(sdm_plan_pivots(p, nskip, skip_idx, skip_val, nadd, add_idx, add_val));
+  SDM_CATCH
+}
+
+static int solve_common(bool fw, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr,
+                         const sdm_int *perm, sdm_int nsuper, const sdm_int *xsuper, sdm_int nrhs, const double *b,
+                         double *y) {
+  SDM_TRY
+  PlanGuard G; sdm_plan *p = G.p;
+  // the ADA pattern is irrelevant for a solve: use an empty one
+  std::vector<sdm_int> zj(m + 1, 0), idperm;
+  if (!perm) { idperm.resize(m); for (sdm_int i = 0; i < m; i++) idperm[i] = i; perm = idperm.data(); }
+  plan_ok(sdm_plan_set_chol(p, m, Ljc, Lir, perm, nsuper, xsuper, zj.data(), nullptr));
+  chol_load_factor(p, Lpr);
+  for (sdm_int c = 0; c < nrhs; c++) {
+    SDM_HIP_CHECK(hipMemcpyAsync(p->rhs.p, b + c * m, m * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    plan_ok(fw ? sdm_plan_fwsolve(p) : sdm_plan_bwsolve(p));
+    SDM_HIP_CHECK(hipMemcpyAsync(y + c * m, p->y.p, m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+  }
+  SDM_CATCH
+}
+int sdm_fwblkslv(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, const sdm_int *perm,
+                 sdm_int nsuper, const sdm_int *xsuper, sdm_int nrhs, const double *b, double *y) {
+  return solve_common(true, m, Ljc, Lir, Lpr, perm, nsuper, xsuper, nrhs, b, y);
+}
+int sdm_bwblkslv(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, const sdm_int *perm,
+                 sdm_int nsuper, const sdm_int *xsuper, sdm_int nrhs, const double *b, double *y) {
+  return solve_common(false, m, Ljc, Lir, Lpr, perm, nsuper, xsuper, nrhs, b, y);
+}
+
+// sparse right-hand sides: the pattern (Yjc,Yir) from symbfwblk is closed under the solve, so the
+// dense solve restricted to it gives exactly the entries selfwsolve / selbwsolve define.
+static int solve_sparse(bool fw, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr,
+                         const sdm_int *perm, sdm_int nsuper, const sdm_int *xsuper, sdm_int n, const sdm_int *Bjc,
+                         const sdm_int *Bir, const double *Bpr, const sdm_int *Yjc, const sdm_int *Yir, double *Ypr) {
+  SDM_TRY
+  PlanGuard G; sdm_plan *p = G.p;
+  std::vector<sdm_int> zj(m + 1, 0), idperm(m);
+  for (sdm_int i = 0; i < m; i++) idperm[i] = i;
+  // forward variant maps b through invperm == dense fwblkslv on a dense copy of b (fwblkslv.c:308-309);
+  // backward variant uses no permutation at all (bwblkslv.c:279-291)
+  plan_ok(sdm_plan_set_chol(p, m, Ljc, Lir, fw ? perm : idperm.data(), nsuper, xsuper, zj.data(), nullptr));
+  chol_load_factor(p, Lpr);
+  std::vector<double> col(m), out(m);
+  for (sdm_int c = 0; c < n; c++) {
+    std::fill(col.begin(), col.end(), 0.0);
+    for (sdm_int t = Bjc[c]; t < Bjc[c + 1]; t++) col[Bir[t]] = Bpr[t];
+    SDM_HIP_CHECK(hipMemcpyAsync(p->rhs.p, col.data(), m * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    plan_ok(fw ? sdm_plan_fwsolve(p) : sdm_plan_bwsolve(p));
+    SDM_HIP_CHECK(hipMemcpyAsync(out.data(), p->y.p, m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+    for (sdm_int t = Yjc[c]; t < Yjc[c + 1]; t++) Ypr[t] = out[Yir[t]];
+  }
+  SDM_CATCH
+}
+int sdm_fwblkslv_sparse(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, const sdm_int *perm,
+                        sdm_int nsuper, const sdm_int *xsuper, sdm_int n, const sdm_int *Bjc, const sdm_int *Bir,
+                        const double *Bpr, const sdm_int *Yjc, const sdm_int *Yir, double *Ypr) {
+  return solve_sparse(true, m, Ljc, Lir, Lpr, perm, nsuper, xsuper, n, Bjc, Bir, Bpr, Yjc, Yir, Ypr);
+}
+int sdm_bwblkslv_sparse(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, sdm_int nsuper,
+                        const sdm_int *xsuper, sdm_int n, const sdm_int *Bjc, const sdm_int *Bir, const double *Bpr,
+                        const sdm_int *Yjc, const sdm_int *Yir, double *Ypr) {
+  return solve_sparse(false, m, Ljc, Lir, Lpr, nullptr, nsuper, xsuper, n, Bjc, Bir, Bpr, Yjc, Yir, Ypr);
+}
+
+// ---- invcholfac
+int sdm_invcholfac(const sdm_cone *K, const double *u, const sdm_int *perm, double *y) {
+  SDM_TRY
+  std::vector<int> ns, p32; sdm_int lenud, plen;
+  cone_blocks(K, ns, lenud, plen);
+  if (lenud == 0) return 0;
+  PlanGuard G; sdm_plan *p = G.p;
+  DevBuf<double> du, dy; DevBuf<int> dp, dn, dpo; DevBuf<int64_t> doff;
+  du.upload(u, (size_t)lenud); dy.alloc((size_t)lenud);
+  if (perm) { perm32(perm, ns, p32); dp.upload(p32); }
+  psd_invcholfac(p->stream, du.p, dy.p, perm ? dp.p : nullptr, ns, (int)K->rsdpN, dn, doff, dpo, false);
+  SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+  SDM_HIP_CHECK(hipMemcpy(y, dy.p, (size_t)lenud * sizeof(double), hipMemcpyDeviceToHost));
+  SDM_CATCH
+}
+
+// ---- psdframeit / psdinvjmul in qrK's frames (sdm_cone.hip)
+// the stream of the calling thread's psdframeit / psdinvjmul calls, created once: a new stream per call costs a new hardware queue, milliseconds
+// against calls of a fraction of one (null where streams have no handles: the plan then makes its own)
+static void *frame_stream() {
+  static thread_local hipStream_t s = nullptr;
+  if (!s && hipStreamCreate(&s) != hipSuccess) s = nullptr;
+  return (void *)s;
+}
+static void h2d(double *d, const double *h, int64_t n) { SDM_HIP_CHECK(hipMemcpy(d, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
+static void d2h(double *h, const double *d, int64_t n) { SDM_HIP_CHECK(hipMemcpy(h, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost)); }
+// How every frame / qrK call begins and ends.  K and frame_kind are checked and the orders of K's blocks are in ns; without PSD blocks there is
+// nothing to do (p stays null: the caller returns); else no argument may be missing and the call has a plan on the thread's stream, p.
+struct FrameCall {
+  std::vector<int> ns;
+  sdm_plan *p = nullptr;
+  FrameCall(const char *who, const sdm_cone *K, int frame_kind, bool args_given) {
+    if (!K) throw std::runtime_error("K is null");
+    if (frame_kind != SDM_FRAME_HOUSEHOLDER && frame_kind != SDM_FRAME_EXPLICIT)
+      throw std::runtime_error("frame_kind must be SDM_FRAME_HOUSEHOLDER (0) or SDM_FRAME_EXPLICIT (1)");
+    if (K->sdpN < 0 || K->rsdpN < 0 || K->rsdpN > K->sdpN) throw std::runtime_error("K: 0 <= rsdpN <= length(K.s) expected");
+    sdm_int lenud, plen;
+    cone_blocks(K, ns, lenud, plen);
+    for (int n : ns) if (n < 0) throw std::runtime_error("K.s: negative order");
+    if (std::all_of(ns.begin(), ns.end(), [](int n) { return n == 0; })) return;
+    if (!args_given) throw std::runtime_error(std::string(who) + ": null argument");
+    p = sdm_plan_create(0, frame_stream());
+    if (!p) plan_ok(1);
+  }
+  ~FrameCall() { sdm_plan_destroy(p); }
+  // the one synchronise of the call, then n doubles of the result d -> h
+  void read_back(double *h, const double *d, int64_t n) { SDM_HIP_CHECK(hipStreamSynchronize(p->stream)); d2h(h, d, n); }
+};
+// the explicit frame on the device (qb): uploaded as it is, or expanded from the Householder form (staged in fr)
+static void frame_upload(sdm_plan *p, const ConeTabs &T, const double *frms, int frame_kind, double *qb, double *fr) {
+  if (frame_kind == SDM_FRAME_EXPLICIT) { h2d(qb, frms, T.lenud); return; }
+  h2d(fr, frms, T.lenfr);
+  cone_expand(p, T, fr, qb);
+}
+int sdm_set_frame_lds_budget(sdm_int bytes) {
+  SDM_TRY
+  cone_set_frame_lds_budget(bytes);
+  SDM_CATCH
+}
+// (every call: one stream, ONE device allocation behind the block tables -- T.data, carved below -- and one synchronise before the read-back)
+int sdm_psdframe_explicit(const sdm_cone *K, const double *frms, double *qb) {
+  SDM_TRY
+  FrameCall C("psdframe_explicit", K, SDM_FRAME_HOUSEHOLDER, frms && qb);
+  if (!C.p) return 0;
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 1, 1, 0);
+  double *dq = T.data, *df = dq + T.lenud;
+  frame_upload(C.p, T, frms, SDM_FRAME_HOUSEHOLDER, dq, df);
+  C.read_back(qb, dq, T.lenud);
+  SDM_CATCH
+}
+int sdm_psdframeit(const sdm_cone *K, const double *lab, const double *frms, int frame_kind, double *x) {
+  SDM_TRY
+  FrameCall C("psdframeit", K, frame_kind, lab && frms && x);
+  if (!C.p) return 0;
+  const int hh = frame_kind == SDM_FRAME_HOUSEHOLDER ? 1 : 0;
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 2, hh, 1);
+  double *dq = T.data, *dx = dq + T.lenud, *dl = dx + T.lenud, *df = dl + T.lenlab;
+  h2d(dl, lab, T.lenlab);
+  frame_upload(C.p, T, frms, frame_kind, dq, df);
+  cone_frameit(C.p, T, dq, dl, dx);
+  C.read_back(x, dx, T.lenud);
+  SDM_CATCH
+}
+int sdm_psdinvjmul(const sdm_cone *K, const double *xlab, const double *frms, int frame_kind, const double *y, double *z) {
+  SDM_TRY
+  FrameCall C("psdinvjmul", K, frame_kind, xlab && frms && y && z);
+  if (!C.p) return 0;
+  const int hh = frame_kind == SDM_FRAME_HOUSEHOLDER ? 1 : 0;
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 5, hh, 1);
+  double *dq = T.data, *dy = dq + T.lenud, *t1 = dy + T.lenud, *t2 = t1 + T.lenud, *dz = t2 + T.lenud, *dl = dz + T.lenud, *df = dl + T.lenlab;
+  h2d(dl, xlab, T.lenlab); h2d(dy, y, T.lenud);
+  frame_upload(C.p, T, frms, frame_kind, dq, df);
+  cone_invjmul(C.p, T, dq, dl, dy, t1, t2, dz);
+  C.read_back(z, dz, T.lenud);
+  SDM_CATCH
+}
+// ---- qrK, the producer of those frames (sdm_qrk.hip); the call shape of the N5 entry points above
+int sdm_set_qr_panel_lds_budget(sdm_int bytes) {
+  SDM_TRY
+  qrk_set_panel_lds_budget(bytes);
+  SDM_CATCH
+}
+int sdm_qrk(const sdm_cone *K, const double *x, int frame_kind, double *q, double *r) {
+  SDM_TRY
+  FrameCall C("qrk", K, frame_kind, x && q);
+  if (!C.p) return 0;
+  QrkSteps S; qrk_plan(S, C.ns, (int)K->rsdpN);
+  const int ex = frame_kind == SDM_FRAME_EXPLICIT ? 1 : 0;
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 1 + ex, 1, 0, S.words());
+  double *dr = T.data, *dqb = dr + T.lenud, *dq = dr + (1 + ex) * T.lenud, *area = dq + T.lenfr;
+  h2d(dr, x, T.lenud);
+  qrk_run(C.p, T, S, area, dq, dr);
+  if (ex) cone_expand(C.p, T, dq, dqb);
+  C.read_back(q, ex ? dqb : dq, ex ? T.lenud : T.lenfr);
+  if (r) d2h(r, dr, T.lenud);
+  SDM_CATCH
+}
+}  // extern "C"

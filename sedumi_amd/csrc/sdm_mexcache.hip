@@ -27,161 +27,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 using namespace sdm;
 
 namespace {
 typedef unsigned long long u64;
-constexpr sdm_int SAMPLE = 512;            // words of the sampled hash
-constexpr sdm_int THREADS_FROM = 1 << 20;  // arrays from 1M words (8 MB) on are checksummed by several host threads
-constexpr u64 P1 = 11400714785074694791ull, P2 = 14029467366897019727ull;
-inline u64 rotl(u64 x, int r) { return (x << r) | (x >> (64 - r)); }
-inline u64 lane(u64 acc, u64 v) { return rotl(acc + v * P2, 31) * P1; }
-// every word, position dependent, as eight independent wrap-around sums of 32 x 32 -> 64 bit products: the compiler vectorises
-// it on the host, and -- sums commute -- the same value comes out of a parallel reduction on the device (k_words_checksum:
-// what a gateway leaves in HBM is fingerprinted there instead of by a pass over the host copy) or of several host threads.
-// A change detector, not a cryptographic hash: any single changed word changes its sum.
-#define SDM_CK_C1 {0x9E3779B1u, 0x85EBCA77u, 0xC2B2AE3Du, 0x27D4EB2Fu, 0x165667B1u, 0xD3A2646Du, 0xFD7046C5u, 0xB55A4F09u}
-#define SDM_CK_C2 {0x8DA6B343u, 0xD8163841u, 0xCB1AB31Fu, 0x9F6B3F4Bu, 0xA54FF53Bu, 0x3C6EF373u, 0xBB67AE85u, 0x6A09E667u}
-u64 fold_sums(const u64 *acc, sdm_int n) {
-  u64 h = (u64)n;
-  for (int k = 0; k < 8; k++) h = lane(h, acc[k]);
-  return h;
-}
-// the eight sums over the words [i0, i1) of v (i0 a multiple of 8), added into acc; one body, compiled for the baseline ISA and for
-// AVX2 / AVX-512 (the host of a GPU box has them; picked once at run time)
-#define SDM_CK_BODY                                                                                                          \
-  static const u64 C1[8] = SDM_CK_C1, C2[8] = SDM_CK_C2;                                                                     \
-  u64 a[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                                                                       \
-  sdm_int i = i0;                                                                                                            \
-  for (; i + 8 <= i1; i += 8)                                                                                                \
-    for (int k = 0; k < 8; k++) {                                                                                            \
-      const u64 w = v[i + k];                                                                                                \
-      a[k] += (u64)((unsigned)w ^ (unsigned)i) * C1[k] + (u64)((unsigned)(w >> 32) ^ (unsigned)i) * C2[k];                   \
-    }                                                                                                                        \
-  for (int k = 0; i + k < i1; k++) {                                                                                         \
-    const u64 w = v[i + k];                                                                                                  \
-    a[k] += (u64)((unsigned)w ^ (unsigned)i) * C1[k] + (u64)((unsigned)(w >> 32) ^ (unsigned)i) * C2[k];                     \
-  }                                                                                                                          \
-  for (int k = 0; k < 8; k++) acc[k] += a[k];
-void sums_base(const u64 *v, sdm_int i0, sdm_int i1, u64 *acc) { SDM_CK_BODY }
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__) && !defined(SDM_NO_MULTIVERSION)
-__attribute__((target("avx2"))) void sums_avx2(const u64 *v, sdm_int i0, sdm_int i1, u64 *acc) { SDM_CK_BODY }
-__attribute__((target("avx512f,avx512dq,avx512vl"))) void sums_avx512(const u64 *v, sdm_int i0, sdm_int i1, u64 *acc) { SDM_CK_BODY }
-typedef void (*sums_fn)(const u64 *, sdm_int, sdm_int, u64 *);
-sums_fn pick_sums() {
-  __builtin_cpu_init();
-  if (__builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512dq") && __builtin_cpu_supports("avx512vl")) return sums_avx512;
-  if (__builtin_cpu_supports("avx2")) return sums_avx2;
-  return sums_base;
-}
-const sums_fn sums = pick_sums();
-#else
-#define sums sums_base
-#endif
-void pool_shutdown();
-// A few helper threads for the checksums of arrays from POOL_FROM words on: what a gateway is handed has usually just been written by
-// the DMA engine (or by a memcpy with streaming stores) and comes from DRAM at 8 - 10 GB/s through one core.  The helpers are created
-// at the first such array, sleep on a condition variable in between (woken in ~10 us) and are joined when the cache is torn down.
-constexpr sdm_int POOL_FROM = 1 << 17;     // 128K words = 1 MB
-class SumPool {
-  std::vector<std::thread> th;
-  std::mutex mu;
-  std::condition_variable cv_go, cv_done;
-  const u64 *v = nullptr;
-  sdm_int n = 0, chunk = 0;
-  int nparts = 0, pending = 0;
-  u64 gen = 0;
-  bool stop = false;
-  u64 part[16][8];
-  void worker(int id, u64 seen) {                              // seen: the generation current when the helper was created (by the one thread that advances it)
-    for (;;) {
-      std::unique_lock<std::mutex> lk(mu);
-      cv_go.wait(lk, [&] { return stop || gen != seen; });
-      if (stop) return;
-      seen = gen;
-      const bool mine = id < nparts;
-      const u64 *vv = v; const sdm_int i0 = std::min(n, (sdm_int)id * chunk), i1 = std::min(n, i0 + chunk);
-      lk.unlock();
-      if (mine) { for (int k = 0; k < 8; k++) part[id][k] = 0; sums(vv, i0, i1, part[id]); }
-      lk.lock();
-      if (mine && --pending == 0) cv_done.notify_one();
-    }
-  }
- public:
-  // the eight sums of v[0, n) into acc, by `want` threads (the caller is one of them)
-  void run(const u64 *vp, sdm_int len, int want, u64 *acc) {
-    want = std::max(1, std::min(want, 16));
-    if (th.empty()) { static bool reg = false; if (!reg) { reg = true; std::atexit([] { pool_shutdown(); }); } }   // sleeping helpers are joined before the process ends
-    while ((int)th.size() < want - 1) { const int id = (int)th.size() + 1; const u64 g0 = gen; th.emplace_back([this, id, g0] { worker(id, g0); }); }
-    const sdm_int ch = ((len + want - 1) / want + 7) & ~(sdm_int)7;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      v = vp; n = len; chunk = ch; nparts = want; pending = want - 1; gen++;
-    }
-    cv_go.notify_all();
-    for (int k = 0; k < 8; k++) part[0][k] = 0;
-    sums(vp, 0, std::min(len, ch), part[0]);
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv_done.wait(lk, [&] { return pending == 0; });
-    }
-    for (int t = 0; t < want; t++) for (int k = 0; k < 8; k++) acc[k] += part[t][k];
-  }
-  void shutdown() {
-    { std::lock_guard<std::mutex> lk(mu); stop = true; }
-    cv_go.notify_all();
-    for (auto &t : th) t.join();
-    th.clear(); stop = false;
-  }
-  ~SumPool() { shutdown(); }
-} g_pool;
-void pool_shutdown() { g_pool.shutdown(); }
-int g_threads = -1;        // sdm_mexcache_set_threads: threads of a big checksum (-1: 4 from POOL_FROM words, up to 8 from 1M; never more than the host has)
-sdm_int g_hash_ns = 0, g_hash_calls = 0;      // host time spent in complete checksums since the last clear (stats[13], [14])
-u64 hash_full(const void *pv, sdm_int n) {
-  const u64 *v = (const u64 *)pv;
-  u64 acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const auto t0 = std::chrono::steady_clock::now();
-  int nt = 1;
-  if (n >= POOL_FROM) {
-    const int hw = (int)std::thread::hardware_concurrency();
-    nt = g_threads >= 0 ? g_threads : (n >= THREADS_FROM ? 8 : 4);
-    nt = std::max(1, std::min(nt, std::max(1, hw)));
-  }
-  if (nt <= 1) sums(v, 0, n, acc);
-  else g_pool.run(v, n, nt, acc);
-  g_hash_ns += (sdm_int)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); g_hash_calls++;
-  return fold_sums(acc, n);
-}
-// the same eight sums of n words in device memory, added into acc8 (zeroed by the caller): work-item t owns the words
-// t, t + stride, ... with stride a multiple of 8, i.e. always the same sum
-__global__ void k_words_checksum(const unsigned long long *v, long long n, unsigned long long *acc8) {
-  const unsigned long long C1[8] = SDM_CK_C1, C2[8] = SDM_CK_C2;
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
-  const int k = (int)(t & 7);
-  unsigned long long s = 0;
-  for (long long i = t; i < n; i += stride) {
-    const unsigned long long w = v[i];
-    const unsigned base = (unsigned)(i & ~7ll);
-    s += (unsigned long long)((unsigned)w ^ base) * C1[k] + (unsigned long long)((unsigned)(w >> 32) ^ base) * C2[k];
-  }
-  if (s) atomicAdd(&acc8[k], s);
-}
-u64 hash_sampled(const void *pv, sdm_int n) {                         // always the first and the last word
-  const u64 *v = (const u64 *)pv;
-  if (n <= 0) return 7;
-  const sdm_int step = n <= SAMPLE ? 1 : (n + SAMPLE - 1) / SAMPLE;
-  u64 h = (u64)n;
-  for (sdm_int i = 0; i < n; i += step) h = lane(h, v[i]);
-  return lane(h, v[n - 1]);
-}
 // Checksums a shim has just computed itself while it copied an array (sdm_mexcache_copy_words: the pattern of the array it returns is a copy
 // of its input's -- one pass over the input for both): valid for the gateway call in progress only, dropped when it returns.
 struct Note { const void *p; sdm_int n; u64 sum; };
@@ -210,25 +62,22 @@ struct Finger {
     for (int i = 0; i < 8; i++) if (ok[i].p == p) { ok[i].epoch = g_epoch; return; }
     ok[nok & 7].p = p; ok[nok++ & 7].epoch = g_epoch;
   }
-  void take(const void *p, sdm_int len) {
-    n = len; sample = hash_sampled(p, len); full = hash_full(p, len); g_fullsum_words += len;
-    for (auto &a : ok) a.p = nullptr;
-    nok = 0; verified(p);
-  }
   // the checksum computed elsewhere: on the device copy of the values that have just been downloaded to p.  No address is trusted
   // yet: whoever presents this content has it read completely once (file header)
   void take_with_full(const void *p, sdm_int len, u64 fullhash) {
-    n = len; sample = hash_sampled(p, len); full = fullhash;
+    n = len; sample = wordsum_sampled(p, len); full = fullhash;
     for (auto &a : ok) a.p = nullptr;
     nok = 0;
   }
+  // ... computed here, by a pass over p: that address is trusted for this epoch
+  void take(const void *p, sdm_int len) { take_with_full(p, len, wordsum_full(p, len)); g_fullsum_words += len; verified(p); }
   bool same(const void *p, sdm_int len) {
     if (len != n || n < 0) return false;
-    if (!strict && len > full_below && trusted(p)) return hash_sampled(p, len) == sample;   // the shortcut of the file header
+    if (!strict && len > full_below && trusted(p)) return wordsum_sampled(p, len) == sample;   // the shortcut of the file header
     u64 sum = 0;
     bool noted = false;
     for (int i = 0; i < g_nnotes; i++) if (g_notes[i].p == p && g_notes[i].n == len) { sum = g_notes[i].sum; noted = true; }
-    if (!noted) { g_fullsum_words += len; sum = hash_full(p, len); }
+    if (!noted) { g_fullsum_words += len; sum = wordsum_full(p, len); }
     if (sum != full) return false;
     verified(p);
     return true;
@@ -287,51 +136,50 @@ enum { ST_ADA_BUILD = 0, ST_ADA_REUSE = 1, ST_ADA_UPLOAD = 2, ST_ADA_RESIDENT = 
        ST_X_UPLOAD = 6, ST_X_RESIDENT = 7, ST_SOLVE_RESIDENT = 8, ST_SOLVE_STATELESS = 9, ST_AT_UPLOAD = 10 };
 
 int device() { const char *dev = getenv("SEDUMI_HIP_DEVICE"); return dev ? atoi(dev) : 0; }
-sdm_plan *new_plan() {
-  sdm_plan *p = sdm_plan_create(device(), nullptr);
-  if (!p) throw std::runtime_error(sdm_last_error());
-  return p;
+sdm_plan *new_plan() { sdm_plan *p = sdm_plan_create(device(), nullptr); if (!p) plan_ok(1); return p; }
+bool vec_is(const std::vector<sdm_int> &v, const sdm_int *p, sdm_int n) {
+  return (sdm_int)v.size() == n && (n == 0 || memcmp(v.data(), p, (size_t)n * sizeof(sdm_int)) == 0);
 }
 
-// ---- one slot per getada gateway: the plan that holds its slice of the problem, and what it was built from
+// ---- one slot per getada gateway: the plan that holds its slice of the problem, and what it was built from.  SlotKey: what a gateway
+// states about the call in progress -- its slot's plan is good for it if all of this is what the plan was built from
+struct SlotKey {
+  u64 pat_ada, pat_a, pat_q;                   // interned patterns of ADA', At and DAt.q (0: not part of this gateway's plan)
+  std::vector<sdm_int> ints;                   // m first, then the scalar and small-vector arguments (cone, block starts)
+  const sdm_int *split;                        // Ajc1 / Ajc2, m entries (null: none)
+  const double *apr; sdm_int napr;             // the values of At (null: the plan does not hold At)
+};
 struct AdaSlot {
   sdm_plan *plan = nullptr;
   bool built = false;
   u64 pat_ada = 0, pat_a = 0, pat_q = 0;
   Finger apr;
-  std::vector<sdm_int> split, ints, perm;      // Ajc1 / Ajc2; the scalar and small-vector arguments (cone, block starts); the last permutation
+  std::vector<sdm_int> split, ints, perm;      // as in SlotKey; perm: the last permutation
   DevBuf<int> invperm;
   void drop() { if (plan) sdm_plan_destroy(plan); plan = nullptr; built = false; perm.clear(); invperm.release(); }
   void set_perm(const sdm_int *pm, sdm_int m) {
-    if ((sdm_int)perm.size() == m && (m == 0 || memcmp(perm.data(), pm, (size_t)m * sizeof(sdm_int)) == 0) && invperm.p) return;
+    if (vec_is(perm, pm, m) && invperm.p) return;
     gw_upload_invperm(invperm, pm, m);
     perm.assign(pm, pm + m);
+  }
+  // the cheap comparisons first: the content check of At's values is paid only when everything else matches
+  bool built_from(const SlotKey &k) {
+    return built && pat_ada == k.pat_ada && pat_a == k.pat_a && pat_q == k.pat_q && ints == k.ints &&
+           (!k.split || vec_is(split, k.split, k.ints[0])) && (!k.apr || apr.same(k.apr, k.napr));
   }
 };
 AdaSlot g_s1, g_s2, g_s3, g_s0;
 
 // whose ada_val holds the ADA values most recently handed back to the host, and what they were
 struct { sdm_plan *plan = nullptr; Finger vals; bool zero = false; } g_last;   // zero: those values are known to be all zero (getada1 with nothing to add)
-DevBuf<u64> g_ck;                       // eight device words: checksum of values a gateway leaves in HBM (k_words_checksum)
 double *g_pin = nullptr;                // pinned staging for the solves' right-hand side and solution (sdm_mexcache_solve)
 sdm_int g_pin_n = 0;
-u64 *g_ck_host = nullptr;               // ... and where they land on the host: pinned, so that the copy is queued like the rest and the one
-                                        // synchronisation of the gateway (its download) covers it (to pageable memory every copy blocked the host)
-// the eight sums of n device words -> g_ck_host, queued on the plan's stream: valid once the stream has been drained
-void device_checksum(sdm_plan *p, const double *v, sdm_int n) {
-  if (!g_ck.p) g_ck.alloc(8);
-  if (!g_ck_host) SDM_HIP_CHECK(hipHostMalloc((void **)&g_ck_host, 8 * sizeof(u64), 0));
-  const sdm_int wg = std::min<sdm_int>(2048, std::max<sdm_int>(64, n / 8192));
-  SDM_HIP_CHECK(hipMemsetAsync(g_ck.p, 0, 8 * sizeof(u64), p->stream));
-  SDM_LAUNCH(k_words_checksum, dim3((unsigned)wg), dim3(256), 0, p->stream, (const unsigned long long *)v, (long long)n, g_ck.p);
-  SDM_HIP_CHECK(hipMemcpyAsync(g_ck_host, g_ck.p, 8 * sizeof(u64), hipMemcpyDeviceToHost, p->stream));
-}
 // ADA' values and absd of plan p -> the host arrays the shim returns, together with the checksum of the values summed on the device:
 // the array at pr is, from now on, known to hold what p->ada_val holds
 void download_returned(sdm_plan *p, double *pr, double *absd, sdm_int nnz) {
-  device_checksum(p, p->ada_val.p, nnz);
+  wordsum_device(p, p->ada_val.p, nnz);
   gw_download(p, pr, absd);                                           // (drains the stream)
-  g_last.plan = p; g_last.vals.take_with_full(pr, nnz, fold_sums(g_ck_host, nnz)); g_last.zero = false;
+  g_last.plan = p; g_last.vals.take_with_full(pr, nnz, wordsum_device_result(nnz)); g_last.zero = false;
   g_tok.serial = 0;                                                   // real arrays went out: a token issued earlier is stale from here on (refused loudly)
 }
 // a gateway leaves its ADA' on the device and hands out a token for it (lazy mode)
@@ -342,34 +190,43 @@ double returned_token(sdm_plan *p, u64 pat, sdm_int m, sdm_int nnz) {
   remember_token(g_tok.serial, pat, m, nnz);
   return LAZY_BASE + (double)g_tok.serial;
 }
-// the pattern id of the ADA' a token stands for; throws unless it is the current token
-u64 token_pattern(double tok, sdm_int m) {
+// what a getada gateway hands back: a token for the ADA' it leaves on the device (absd is real all the same), or the arrays
+void hand_back(sdm_plan *p, u64 pat, sdm_int m, sdm_int nnz, double *ADApr, double *absd, double *token_out) {
+  if (!token_out) { download_returned(p, ADApr, absd, nnz); return; }
+  if (absd) gw_download(p, nullptr, absd);
+  *token_out = returned_token(p, pat, m, nnz);
+}
+// the pattern id of the ADA' a token stands for.  TOKEN_CURRENT: throws unless it is the current token; TOKEN_LAST_16 (getada1.mex: pattern
+// only): any of the last sixteen handed out
+enum TokenAge { TOKEN_CURRENT, TOKEN_LAST_16 };
+u64 token_pattern(double tok, sdm_int m, TokenAge age) {
+  if (age == TOKEN_LAST_16) {
+    if (is_token(tok)) {
+      const u64 serial = (u64)(tok - LAZY_BASE);
+      const TokRec &r = g_tok_hist[serial & 15];
+      if (serial != 0 && r.serial == serial && r.m == m) return r.pat;
+    }
+    throw std::runtime_error("lazy ADA token is not one of the last sixteen handed out (SEDUMI_HIP_LAZY: getada1 needs the pattern behind the token it is given)");
+  }
   if (!g_last.plan || !is_token(tok) || tok != LAZY_BASE + (double)g_tok.serial || g_tok.m != m)
     throw std::runtime_error("lazy ADA token is not the current one (SEDUMI_HIP_LAZY: the array a getada gateway returned must be handed to the next gateway untouched)");
   return g_tok.pat;
 }
-// the pattern id behind ANY of the last sixteen tokens (getada1.mex: pattern only); throws when it is not remembered
-u64 token_pattern_any(double tok, sdm_int m) {
-  if (is_token(tok)) {
-    const u64 serial = (u64)(tok - LAZY_BASE);
-    const TokRec &r = g_tok_hist[serial & 15];
-    if (serial != 0 && r.serial == serial && r.m == m) return r.pat;
-  }
-  throw std::runtime_error("lazy ADA token is not one of the last sixteen handed out (SEDUMI_HIP_LAZY: getada1 needs the pattern behind the token it is given)");
+// ... and its host copy.  Looked up when the gateway's other patterns have been interned: an intern() may have pushed it out of g_pat
+const Pattern &cached_pattern(u64 id) {
+  const Pattern *pp = pattern_by_id(id);
+  if (!pp || pp->irc.empty()) throw std::runtime_error("lazy ADA token: its pattern is not cached any more");
+  return *pp;
 }
-void ada_input_token(sdm_plan *p, sdm_int nnz) {
-  g_stat[ST_ADA_RESIDENT]++;
+// ADA' from the plan that holds it (g_last.plan) -> p->ada_val; counted as `stat`
+void take_resident(sdm_plan *p, sdm_int nnz, int stat) {
+  g_stat[stat]++;
   if (g_last.plan != p)
     SDM_HIP_CHECK(hipMemcpyAsync(p->ada_val.p, g_last.plan->ada_val.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
 }
-// the input values of a gateway -> p->ada_val: from the device if they are what the previous gateway returned, else from the host
-void ada_input(sdm_plan *p, const double *pr, sdm_int nnz) {
-  if (g_last.plan && g_last.vals.same(pr, nnz)) {
-    g_stat[ST_ADA_RESIDENT]++;
-    if (g_last.plan != p)
-      SDM_HIP_CHECK(hipMemcpyAsync(p->ada_val.p, g_last.plan->ada_val.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
-    return;
-  }
+// the input values of a gateway -> p->ada_val: from the device if they are a token's, or what the previous gateway returned, else from the host
+void ada_input(sdm_plan *p, bool token, const double *pr, sdm_int nnz) {
+  if (token || (g_last.plan && g_last.vals.same(pr, nnz))) { take_resident(p, nnz, ST_ADA_RESIDENT); return; }
   g_stat[ST_ADA_UPLOAD]++;
   SDM_HIP_CHECK(hipMemcpyAsync(p->ada_val.p, pr, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, p->stream));
 }
@@ -391,13 +248,11 @@ void drop_chol() {
 void drop_all() {
   for (AdaSlot *s : {&g_s1, &g_s2, &g_s3, &g_s0}) { if (s->plan) forget_plan(s->plan); s->drop(); }
   drop_chol();
-  g_pool.shutdown();
-  g_ck.release();
-  if (g_ck_host) { (void)hipHostFree(g_ck_host); g_ck_host = nullptr; }
+  wordsum_shutdown();
   if (g_pin) { (void)hipHostFree(g_pin); g_pin = nullptr; g_pin_n = 0; }
   for (auto &p : g_pat) p = Pattern();
   for (auto &t : g_tok_hist) t = TokRec();
-  g_fullsum_words = 0; g_hash_ns = 0; g_hash_calls = 0;
+  g_fullsum_words = 0;
 }
 void at_exit_once() {
   // the cached plans own streams, events and device memory: they go before the HIP runtime's own exit handlers run (registered
@@ -406,8 +261,21 @@ void at_exit_once() {
   static bool done = false;
   if (!done) { done = true; std::atexit([] { drop_all(); }); }
 }
-bool vec_is(const std::vector<sdm_int> &v, const sdm_int *p, sdm_int n) {
-  return (sdm_int)v.size() == n && (n == 0 || memcmp(v.data(), p, (size_t)n * sizeof(sdm_int)) == 0);
+
+// the slot's plan for the call `k` describes: kept, or built again by `build` (which uploads At where the plan holds it)
+template <class Build> void refresh(AdaSlot &S, const SlotKey &k, Build build) {
+  if (S.built_from(k)) { g_stat[ST_ADA_REUSE]++; return; }
+  if (!S.plan) S.plan = new_plan();
+  at_exit_once();
+  S.built = false; forget_plan(S.plan);
+  g_stat[ST_ADA_BUILD]++;
+  if (k.apr) g_stat[ST_AT_UPLOAD]++;
+  build(S.plan);
+  S.pat_ada = k.pat_ada; S.pat_a = k.pat_a; S.pat_q = k.pat_q; S.ints = k.ints;
+  if (k.split) S.split.assign(k.split, k.split + k.ints[0]);
+  if (k.apr) S.apr.take(k.apr, k.napr);
+  S.perm.clear();                              // (getada1 / getada2: the new plan's triangle is filled by the next set_perm)
+  S.built = true;
 }
 
 sdm_plan *chol_plan(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const sdm_int *perm, sdm_int nsuper, const sdm_int *xsuper,
@@ -423,14 +291,10 @@ sdm_plan *chol_plan(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const sdm
   g.pat_l = pl; g.pat_x = px; g.perm.assign(perm, perm + m); g.xsuper.assign(xsuper, xsuper + nsuper + 1);
   return g.plan;
 }
-
-#define MC_TRY try { SDM_HIP_CHECK(hipSetDevice(device()));
-#define MC_CATCH                                                    \
-  drop_notes();                                                     \
-  }                                                                 \
-  catch (const std::exception &e) { drop_notes(); set_error(e.what()); return 1; } \
-  catch (...) { drop_notes(); set_error("unknown error"); return 1; }             \
-  return 0;
+// a gateway's body: the shared try / catch, on the cache's device, with the shims' notes dropped however it ends
+struct NotesScope { ~NotesScope() { drop_notes(); } };
+#define MC_TRY SDM_TRY NotesScope notes_scope; SDM_HIP_CHECK(hipSetDevice(device()));
+#define MC_CATCH SDM_CATCH
 }  // namespace
 
 extern "C" {
@@ -441,35 +305,19 @@ void sdm_mexcache_forget_notes(void) { drop_notes(); }
 // cache then does not read src a second time to check it (a shim copies the pattern of its input into the array it returns anyway)
 unsigned long long sdm_mexcache_copy_words(void *dst, const void *src, sdm_int n) {
   u64 sum;
-  if (n >= POOL_FROM) { memcpy(dst, src, (size_t)n * 8); sum = hash_full(src, n); g_fullsum_words += n; }
-  else {
-    const u64 *v = (const u64 *)src; u64 *o = (u64 *)dst;
-    static const u64 C1[8] = SDM_CK_C1, C2[8] = SDM_CK_C2;
-    u64 a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    sdm_int i = 0;
-    for (; i + 8 <= n; i += 8)
-      for (int k = 0; k < 8; k++) {
-        const u64 w = v[i + k];
-        o[i + k] = w;
-        a[k] += (u64)((unsigned)w ^ (unsigned)i) * C1[k] + (u64)((unsigned)(w >> 32) ^ (unsigned)i) * C2[k];
-      }
-    for (int k = 0; i + k < n; k++) {
-      const u64 w = v[i + k];
-      o[i + k] = w;
-      a[k] += (u64)((unsigned)w ^ (unsigned)i) * C1[k] + (u64)((unsigned)(w >> 32) ^ (unsigned)i) * C2[k];
-    }
-    sum = fold_sums(a, n);
-  }
+  if (n >= WORDSUM_POOL_FROM) { memcpy(dst, src, (size_t)n * 8); sum = wordsum_full(src, n); g_fullsum_words += n; }
+  else sum = wordsum_copy(dst, src, n);
   if (g_nnotes < 4) g_notes[g_nnotes++] = Note{src, n, sum};
   return sum;
 }
 // the content checksum of n 8-byte words on the host (what residency is decided on; tests, and the bench's statement of its cost)
-unsigned long long sdm_mexcache_checksum(const void *words, sdm_int n) { return hash_full(words, n); }
+unsigned long long sdm_mexcache_checksum(const void *words, sdm_int n) { return wordsum_full(words, n); }
 // on != 0: every presentation of every array is checksummed completely (no address is ever trusted) -- for callers that edit arrays
 // IN PLACE between gateway calls of one iteration (sedumi.m never does); costs a pass over the host array per call
 void sdm_mexcache_set_strict(int on) { strict = on != 0; }
 void sdm_mexcache_stats(sdm_int *out, sdm_int n) {
-  g_stat[11] = g_fullsum_words; g_stat[12] = (sdm_int)g_epoch; g_stat[13] = g_hash_ns; g_stat[14] = g_hash_calls;
+  g_stat[11] = g_fullsum_words; g_stat[12] = (sdm_int)g_epoch;
+  wordsum_host_time(&g_stat[13], &g_stat[14]);
   for (sdm_int i = 0; i < n && i < 16; i++) out[i] = g_stat[i];
 }
 // arrays of up to `words` words are checksummed completely at every presentation (default 65 536); larger ones once per address and epoch
@@ -479,46 +327,36 @@ void sdm_mexcache_set_lazy(int level) { g_lazy = level < 0 ? -1 : std::min(level
 int sdm_mexcache_lazy(void) { return lazy_level(); }
 // m x m of the ADA' a token stands for and its number of nonzeros; returns 1 (with sdm_last_error) unless `token` is the current token
 int sdm_mexcache_token_info(double token, sdm_int m, sdm_int *nnz) {
-  try { token_pattern(token, m); *nnz = g_tok.nnz; return 0; } catch (const std::exception &e) { set_error(e.what()); return 1; }
+  SDM_TRY token_pattern(token, m, TOKEN_CURRENT); *nnz = g_tok.nnz; SDM_CATCH
 }
 // the pattern behind the current token into the caller's arrays (m + 1 and nnz entries)
 int sdm_mexcache_token_pattern(double token, sdm_int m, sdm_int *jc_out, sdm_int *ir_out) {
-  try {
-    Pattern *pp = pattern_by_id(token_pattern(token, m));
-    if (!pp || pp->irc.empty()) throw std::runtime_error("lazy ADA token: its pattern is not cached any more");
-    memcpy(jc_out, pp->jcc.data(), pp->jcc.size() * sizeof(sdm_int)); memcpy(ir_out, pp->irc.data(), pp->irc.size() * sizeof(sdm_int));
-    return 0;
-  } catch (const std::exception &e) { set_error(e.what()); return 1; }
+  SDM_TRY
+  const Pattern &P = cached_pattern(token_pattern(token, m, TOKEN_CURRENT));
+  memcpy(jc_out, P.jcc.data(), P.jcc.size() * sizeof(sdm_int)); memcpy(ir_out, P.irc.data(), P.irc.size() * sizeof(sdm_int));
+  SDM_CATCH
 }
 double sdm_mexcache_token_base(void) { return LAZY_BASE; }
 // threads of the checksum of an array from 128K words on (the caller's included): -1 = automatic (4, and 8 from 1M words), 1 = none
-void sdm_mexcache_set_threads(int n) { g_threads = n; }
+void sdm_mexcache_set_threads(int n) { wordsum_set_threads(n); }
 
+// ---- the cached getada gateways.  token_in != 0: the ADA' handed in is a lazy token (ADAjc / ADAir / ADApr_in may be NULL: the cache knows the
+// pattern and the device has the values); token_out != NULL: the values stay on the device and *token_out stands for them (ADApr may be NULL)
 // ADA = getada1(ADA, A, Ajc2, perm, d, blkstart) on the cache (same arguments as sdm_getada1)
 int sdm_mexcache_getada1(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, sdm_int N, const sdm_int *Ajc, const sdm_int *Air,
                          const double *Apr, const sdm_int *Ajc2, const sdm_int *perm, sdm_int lpN, const double *dl, sdm_int lorN,
                          const double *ddet, const sdm_int *qblkstart, double *ADApr, double token_in, double *token_out) {
-  // token_in != 0: the ADA' handed in is a lazy token (ADAjc / ADAir may be NULL: only its pattern matters and the cache knows it);
-  // token_out != NULL: the values stay on the device and *token_out stands for them (ADApr may be NULL)
   MC_TRY
+  // (only the pattern of the input matters -- the result starts from zero, getada1.c:222-225 -- so a token that is no longer current will do)
+  const u64 pa = token_in != 0.0 ? token_pattern(token_in, m, TOKEN_LAST_16) : intern(m, ADAjc, ADAir), pA = intern(m, Ajc, Air);
+  if (token_in != 0.0) { const Pattern &P = cached_pattern(pa); ADAjc = P.jcc.data(); ADAir = P.irc.data(); }
+  SlotKey key = {pa, pA, 0, {m, N, lpN, lorN}, Ajc2, Apr, Ajc[m]};
+  key.ints.insert(key.ints.end(), qblkstart, qblkstart + lorN + 1);
   AdaSlot &S = g_s1;
-  const u64 pa = token_in != 0.0 ? token_pattern_any(token_in, m) : intern(m, ADAjc, ADAir), pA = intern(m, Ajc, Air);
-  if (token_in != 0.0) { Pattern *pp = pattern_by_id(pa); if (!pp || pp->irc.empty()) throw std::runtime_error("lazy ADA token: its pattern is not cached any more"); ADAjc = pp->jcc.data(); ADAir = pp->irc.data(); }
-  std::vector<sdm_int> ints = {m, N, lpN, lorN};
-  ints.insert(ints.end(), qblkstart, qblkstart + lorN + 1);
-  if (!(S.built && S.pat_ada == pa && S.pat_a == pA && S.ints == ints && vec_is(S.split, Ajc2, m) && S.apr.same(Apr, Ajc[m]))) {
-    if (!S.plan) S.plan = new_plan();
-    at_exit_once();
-    S.built = false; forget_plan(S.plan);
-    g_stat[ST_ADA_BUILD]++; g_stat[ST_AT_UPLOAD]++;
-    gw_build_getada1(S.plan, m, ADAjc, ADAir, Ajc, Air, Apr, Ajc2, lpN, lorN, qblkstart);
-    S.pat_ada = pa; S.pat_a = pA; S.ints = ints; S.split.assign(Ajc2, Ajc2 + m); S.apr.take(Apr, Ajc[m]); S.perm.clear();
-    S.built = true;
-  } else g_stat[ST_ADA_REUSE]++;
+  refresh(S, key, [&](sdm_plan *p) { gw_build_getada1(p, m, ADAjc, ADAir, Ajc, Air, Apr, Ajc2, lpN, lorN, qblkstart); });
   S.set_perm(perm, m);
   gw_run_getada1(S.plan, S.invperm.p, dl, ddet);
-  if (token_out) *token_out = returned_token(S.plan, pa, m, ADAjc[m]);
-  else download_returned(S.plan, ADApr, nullptr, ADAjc[m]);
+  hand_back(S.plan, pa, m, ADAjc[m], ADApr, nullptr, token_out);
   g_last.zero = gw_getada1_is_zero(S.plan);
   MC_CATCH
 }
@@ -527,25 +365,16 @@ int sdm_mexcache_getada1(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, 
 int sdm_mexcache_getada2(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, const double *ADApr_in, double *ADApr, sdm_int lorN,
                          const sdm_int *Qjc, const sdm_int *Qir, const double *Qpr, const sdm_int *qperm, double token_in, double *token_out) {
   MC_TRY
+  const u64 pa = token_in != 0.0 ? token_pattern(token_in, m, TOKEN_CURRENT) : intern(m, ADAjc, ADAir), pq = intern(m, Qjc, Qir);
+  if (token_in != 0.0) { const Pattern &P = cached_pattern(pa); ADAjc = P.jcc.data(); ADAir = P.irc.data(); }
+  const SlotKey key = {pa, 0, pq, {m, lorN}, nullptr, nullptr, 0};
   AdaSlot &S = g_s2;
-  const u64 pa = token_in != 0.0 ? token_pattern(token_in, m) : intern(m, ADAjc, ADAir), pq = intern(m, Qjc, Qir);
-  if (token_in != 0.0) { Pattern *pp = pattern_by_id(pa); if (!pp || pp->irc.empty()) throw std::runtime_error("lazy ADA token: its pattern is not cached any more"); ADAjc = pp->jcc.data(); ADAir = pp->irc.data(); }
-  std::vector<sdm_int> ints = {m, lorN};
-  if (!(S.built && S.pat_ada == pa && S.pat_q == pq && S.ints == ints)) {
-    if (!S.plan) S.plan = new_plan();
-    at_exit_once();
-    S.built = false; forget_plan(S.plan);
-    g_stat[ST_ADA_BUILD]++;
-    gw_build_getada2(S.plan, m, ADAjc, ADAir, lorN, Qjc, Qir);
-    S.pat_ada = pa; S.pat_q = pq; S.ints = ints; S.perm.clear();
-    S.built = true;
-  } else g_stat[ST_ADA_REUSE]++;
+  refresh(S, key, [&](sdm_plan *p) { gw_build_getada2(p, m, ADAjc, ADAir, lorN, Qjc, Qir); });
   S.set_perm(qperm, m);
-  if (token_in != 0.0) ada_input_token(S.plan, ADAjc[m]); else ada_input(S.plan, ADApr_in, ADAjc[m]);
+  ada_input(S.plan, token_in != 0.0, ADApr_in, ADAjc[m]);
   g_last.zero = false;                                                // (Lorentz terms are being added)
   gw_run_getada2(S.plan, S.invperm.p, Qpr);
-  if (token_out) *token_out = returned_token(S.plan, pa, m, ADAjc[m]);
-  else download_returned(S.plan, ADApr, nullptr, ADAjc[m]);
+  hand_back(S.plan, pa, m, ADAjc[m], ADApr, nullptr, token_out);
   MC_CATCH
 }
 // [ADA, absd] = getada3(ADA, A, Ajc1, Aord, udsqr, K)
@@ -553,29 +382,20 @@ int sdm_mexcache_getada3(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, 
                          const sdm_int *Ajc, const sdm_int *Air, const double *Apr, const sdm_int *Ajc1, const double *udsqr,
                          const sdm_cone *K, const sdm_int *psd_blkstart, double *absd, double token_in, double *token_out) {
   MC_TRY
+  const u64 pa = token_in != 0.0 ? token_pattern(token_in, m, TOKEN_CURRENT) : intern(m, ADAjc, ADAir), pA = intern(m, Ajc, Air);
+  if (token_in != 0.0) { const Pattern &P = cached_pattern(pa); ADAjc = P.jcc.data(); ADAir = P.irc.data(); }
+  SlotKey key = {pa, pA, 0, {m, N, K->lorN, K->sdpN, K->rsdpN}, Ajc1, Apr, Ajc[m]};
+  key.ints.insert(key.ints.end(), K->sdpNL, K->sdpNL + K->sdpN);
+  key.ints.insert(key.ints.end(), psd_blkstart, psd_blkstart + K->sdpN + (K->sdpN > 0 ? 1 : 0));
   AdaSlot &S = g_s3;
-  const u64 pa = token_in != 0.0 ? token_pattern(token_in, m) : intern(m, ADAjc, ADAir), pA = intern(m, Ajc, Air);
-  if (token_in != 0.0) { Pattern *pp = pattern_by_id(pa); if (!pp || pp->irc.empty()) throw std::runtime_error("lazy ADA token: its pattern is not cached any more"); ADAjc = pp->jcc.data(); ADAir = pp->irc.data(); }
-  std::vector<sdm_int> ints = {m, N, K->lorN, K->sdpN, K->rsdpN};
-  ints.insert(ints.end(), K->sdpNL, K->sdpNL + K->sdpN);
-  ints.insert(ints.end(), psd_blkstart, psd_blkstart + K->sdpN + (K->sdpN > 0 ? 1 : 0));
-  if (!(S.built && S.pat_ada == pa && S.pat_a == pA && S.ints == ints && vec_is(S.split, Ajc1, m) && S.apr.same(Apr, Ajc[m]))) {
-    if (!S.plan) S.plan = new_plan();
-    at_exit_once();
-    S.built = false; forget_plan(S.plan);
-    g_stat[ST_ADA_BUILD]++; g_stat[ST_AT_UPLOAD]++;
-    gw_build_getada3(S.plan, m, ADAjc, ADAir, N, Ajc, Air, Apr, Ajc1, K, psd_blkstart);
-    S.pat_ada = pa; S.pat_a = pA; S.ints = ints; S.split.assign(Ajc1, Ajc1 + m); S.apr.take(Apr, Ajc[m]);
-    S.built = true;
-  } else g_stat[ST_ADA_REUSE]++;
+  refresh(S, key, [&](sdm_plan *p) { gw_build_getada3(p, m, ADAjc, ADAir, N, Ajc, Air, Apr, Ajc1, K, psd_blkstart); });
   const sdm_int up0 = g_stat[ST_ADA_UPLOAD];
   const bool was_zero = g_last.zero;
-  if (token_in != 0.0) ada_input_token(S.plan, ADAjc[m]); else ada_input(S.plan, ADApr_in, ADAjc[m]);
+  ada_input(S.plan, token_in != 0.0, ADApr_in, ADAjc[m]);
   const bool zero_in = was_zero && g_stat[ST_ADA_UPLOAD] == up0;      // the device's ADA' was taken, and it is the zero matrix getada1 left
   g_last.zero = false;
   gw_run_getada3(S.plan, udsqr, zero_in);
-  if (token_out) { gw_download(S.plan, nullptr, absd); *token_out = returned_token(S.plan, pa, m, ADAjc[m]); }
-  else download_returned(S.plan, ADApr, absd, ADAjc[m]);
+  hand_back(S.plan, pa, m, ADAjc[m], ADApr, absd, token_out);
   MC_CATCH
 }
 
@@ -584,21 +404,13 @@ int sdm_mexcache_getada(sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, s
                         const double *Apr, sdm_int lpN, const double *dl, sdm_int lorN, const double *ddet, const sdm_int *qblkstart,
                         const sdm_int *Qjc, const sdm_int *Qir, const double *Qpr, double *ADApr, double *absd) {
   MC_TRY
-  AdaSlot &S = g_s0;
   const u64 pa = intern(m, ADAjc, ADAir), pA = intern(m, Ajc, Air), pq = lorN > 0 ? intern(m, Qjc, Qir) : 0;
-  std::vector<sdm_int> ints = {m, N, lpN, lorN};
-  ints.insert(ints.end(), qblkstart, qblkstart + (lorN > 0 ? lorN + 1 : 0));
-  if (!(S.built && S.pat_ada == pa && S.pat_a == pA && S.pat_q == pq && S.ints == ints && S.apr.same(Apr, Ajc[m]))) {
-    if (!S.plan) S.plan = new_plan();
-    at_exit_once();
-    S.built = false; forget_plan(S.plan);
-    g_stat[ST_ADA_BUILD]++; g_stat[ST_AT_UPLOAD]++;
-    gw_build_getada(S.plan, m, ADAjc, ADAir, Ajc, Air, Apr, lpN, lorN, qblkstart, Qjc, Qir);
-    S.pat_ada = pa; S.pat_a = pA; S.pat_q = pq; S.ints = ints; S.apr.take(Apr, Ajc[m]);
-    S.built = true;
-  } else g_stat[ST_ADA_REUSE]++;
+  SlotKey key = {pa, pA, pq, {m, N, lpN, lorN}, nullptr, Apr, Ajc[m]};
+  key.ints.insert(key.ints.end(), qblkstart, qblkstart + (lorN > 0 ? lorN + 1 : 0));
+  AdaSlot &S = g_s0;
+  refresh(S, key, [&](sdm_plan *p) { gw_build_getada(p, m, ADAjc, ADAir, Ajc, Air, Apr, lpN, lorN, qblkstart, Qjc, Qir); });
   gw_run_getada(S.plan, dl, ddet, Qpr);
-  download_returned(S.plan, ADApr, absd, ADAjc[m]);
+  hand_back(S.plan, pa, m, ADAjc[m], ADApr, absd, nullptr);
   MC_CATCH
 }
 
@@ -610,30 +422,27 @@ int sdm_mexcache_blkchol(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, cons
   // token_in != 0: X is a lazy token (level 2: Xjc / Xir / Xpr may be NULL)
   MC_TRY
   // X is what getada3 returned in the epoch that ends here: its values and pattern are looked at before the epoch advances
-  const u64 px = token_in != 0.0 ? token_pattern(token_in, m) : intern(m, Xjc, Xir);
-  if (token_in != 0.0) { Pattern *pp = pattern_by_id(px); if (!pp || pp->irc.empty()) throw std::runtime_error("lazy ADA token: its pattern is not cached any more"); Xjc = pp->jcc.data(); Xir = pp->irc.data(); }
+  const u64 px = token_in != 0.0 ? token_pattern(token_in, m, TOKEN_CURRENT) : intern(m, Xjc, Xir);
+  if (token_in != 0.0) { const Pattern &P = cached_pattern(px); Xjc = P.jcc.data(); Xir = P.irc.data(); }
   const sdm_int nnzX = Xjc[m], nnzL = Ljc[m];
   const bool x_resident = token_in != 0.0 || (g_last.plan && g_last.vals.same(Xpr, nnzX));
   g_epoch++;                         // a new factor: every address trusted so far has to present its complete content again (file header)
   sdm_plan *p = chol_plan(m, Ljc, Lir, perm, nsuper, xsuper, Xjc, Xir, px);
   g.have_factor = false;             // the resident factor is about to be overwritten: whatever the solves are handed before this call has returned is not it
-  if (x_resident) {
-    g_stat[ST_X_RESIDENT]++;
-    if (g_last.plan != p)
-      SDM_HIP_CHECK(hipMemcpyAsync(p->ada_val.p, g_last.plan->ada_val.p, (size_t)nnzX * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
-  } else {
+  if (x_resident) take_resident(p, nnzX, ST_X_RESIDENT);
+  else {
     g_stat[ST_X_UPLOAD]++;
     SDM_HIP_CHECK(hipMemcpyAsync(p->ada_val.p, Xpr, (size_t)nnzX * sizeof(double), hipMemcpyHostToDevice, p->stream));
   }
   if (absd) SDM_HIP_CHECK(hipMemcpyAsync(p->absd.p, absd, (size_t)m * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  if (sdm_plan_blkchol_wait(p, pars, absd ? 1 : 0)) throw std::runtime_error(sdm_last_error());   // (waited for, repeated once on the launch-per-panel path after a time-out)
+  plan_ok(sdm_plan_blkchol_wait(p, pars, absd ? 1 : 0));   // (waited for, repeated once on the launch-per-panel path after a time-out)
   // L.L values, L.d and the fingerprint of the factor (summed on the device: no pass over the host copy) in one drain of the stream
   chol_extract(p, p->lpr.p);
-  device_checksum(p, p->lpr.p, nnzL);
+  wordsum_device(p, p->lpr.p, nnzL);
   SDM_HIP_CHECK(hipMemcpyAsync(Lpr, p->lpr.p, (size_t)nnzL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   SDM_HIP_CHECK(hipMemcpyAsync(d, p->chol.d.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-  if (sdm_plan_pivots(p, nskip, skip_idx, skip_val, nadd, add_idx, add_val)) throw std::runtime_error(sdm_last_error());   // (drains the stream)
-  g.lpr.take_with_full(Lpr, nnzL, fold_sums(g_ck_host, nnzL));
+  plan_ok(sdm_plan_pivots(p, nskip, skip_idx, skip_val, nadd, add_idx, add_val));   // (drains the stream)
+  g.lpr.take_with_full(Lpr, nnzL, wordsum_device_result(nnzL));
   g.have_factor = true;
   MC_CATCH
 }
@@ -643,16 +452,13 @@ int sdm_mexcache_blkchol(sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, cons
 int sdm_mexcache_solve(int fw, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const double *Lpr, const sdm_int *perm, sdm_int nsuper,
                        const sdm_int *xsuper, sdm_int nrhs, const double *b, double *y) {
   MC_TRY
-  bool hit = g.plan && g.have_factor && vec_is(g.xsuper, xsuper, nsuper + 1) && (!perm || vec_is(g.perm, perm, m));
-  hit = hit && intern(m, Ljc, Lir) == g.pat_l && g.lpr.same(Lpr, Ljc[m]);
-  if (!hit) {
+  sdm_plan *p = sdm_mexcache_factor_plan(m, Ljc, Lir, Lpr, perm, nsuper, xsuper);
+  if (!p) {
     g_stat[ST_SOLVE_STATELESS]++;
-    if ((fw ? sdm_fwblkslv : sdm_bwblkslv)(m, Ljc, Lir, Lpr, perm, nsuper, xsuper, nrhs, b, y)) throw std::runtime_error(sdm_last_error());
-    drop_notes();
+    plan_ok((fw ? sdm_fwblkslv : sdm_bwblkslv)(m, Ljc, Lir, Lpr, perm, nsuper, xsuper, nrhs, b, y));
     return 0;
   }
   g_stat[ST_SOLVE_RESIDENT]++;
-  sdm_plan *p = g.plan;
   // right-hand side and solution travel through a pinned buffer: copies between pageable host memory and the device block the host once
   // each, and a solve of a small factor is two such copies around 10 us of kernels
   if (g_pin_n < 2 * m) {
@@ -664,12 +470,12 @@ int sdm_mexcache_solve(int fw, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir
   for (sdm_int c = 0; c < nrhs; c++) {
     memcpy(g_pin, b + c * m, (size_t)m * sizeof(double));
     SDM_HIP_CHECK(hipMemcpyAsync(p->rhs.p, g_pin, (size_t)m * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    if (fw ? sdm_plan_fwsolve(p) : sdm_plan_bwsolve(p)) throw std::runtime_error(sdm_last_error());
+    plan_ok(fw ? sdm_plan_fwsolve(p) : sdm_plan_bwsolve(p));
     SDM_HIP_CHECK(hipMemcpyAsync(g_pin + m, p->y.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     SDM_HIP_CHECK(hipStreamSynchronize(p->stream));
     memcpy(y + c * m, g_pin + m, (size_t)m * sizeof(double));
   }
-  if (sdm_plan_sync(p)) throw std::runtime_error(sdm_last_error());     // (time-out flags of the plan)
+  plan_ok(sdm_plan_sync(p));     // (time-out flags of the plan)
   MC_CATCH
 }
 

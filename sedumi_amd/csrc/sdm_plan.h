@@ -454,6 +454,11 @@ struct PersistTurn {
 #endif
 };
 void set_error(const std::string &msg);
+// an extern "C" entry point's body between SDM_TRY and SDM_CATCH returns 0, or 1 with the thread's last error set (sdm_last_error)
+#define SDM_TRY try {
+#define SDM_CATCH } catch (const std::exception &e) { sdm::set_error(e.what()); return 1; } catch (...) { sdm::set_error("unknown error"); return 1; } return 0;
+// ... and a call of one from inside another: its failure goes on as an exception with the same text
+inline void plan_ok(int rc) { if (rc) throw std::runtime_error(sdm_last_error()); }
 // sdm_chol_build.hip
 void chol_build(sdm_plan *P, sdm_int m, const sdm_int *Ljc, const sdm_int *Lir, const sdm_int *perm,
                 sdm_int nsuper, const sdm_int *xsuper, const sdm_int *ADAjc, const sdm_int *ADAir);
@@ -510,7 +515,7 @@ void dense_tables(DensePlan &D, sdm_int m, sdm_int nden, const sdm_int *dzjc, co
 void dense_prodformfact(sdm_plan *P, hipStream_t st, DensePlan &D, const double *smult, double maxu);   // the product-form factorisation on the device
 void dense_fetch_tables(hipStream_t st, DensePlan &D);
 void dense_prodform(sdm_plan *P, double *y, bool with_divide);       // y <- bwdpr1(Lden, fwdpr1(Lden, y) ./ Ld)   (permuted order)
-// sdm_capi.hip: gateway-shaped plans -- what ONE getada gateway needs (tier 1 builds one per call, sdm_mexcache.hip keeps them)
+// sdm_gateways.hip: gateway-shaped plans -- what ONE getada gateway needs (tier 1 builds one per call, sdm_mexcache.hip keeps them)
 void gw_upload_invperm(DevBuf<int> &buf, const sdm_int *perm, sdm_int m);
 void gw_build_getada1(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int *ADAir, const sdm_int *Ajc, const sdm_int *Air,
                       const double *Apr, const sdm_int *Ajc2, sdm_int lpN, sdm_int lorN, const sdm_int *qblkstart);
@@ -525,6 +530,18 @@ void gw_build_getada(sdm_plan *p, sdm_int m, const sdm_int *ADAjc, const sdm_int
                      sdm_int lpN, sdm_int lorN, const sdm_int *qblkstart, const sdm_int *Qjc, const sdm_int *Qir);
 void gw_run_getada(sdm_plan *p, const double *dl, const double *ddet, const double *Qpr);
 void gw_download(sdm_plan *p, double *ADApr, double *absd);
+void cone_blocks(const sdm_cone *K, std::vector<int> &ns, sdm_int &lenud, sdm_int &plen);   // orders of the PSD blocks, doubles of their matrices, sum of orders
+void perm32(const sdm_int *perm, const std::vector<int> &ns, std::vector<int> &out);        // a permutation per block, checked (sdm_plan_invcholfac too)
+// sdm_wordsum.hip: content checksums of 8-byte words (what sdm_mexcache.hip decides residency on)
+constexpr sdm_int WORDSUM_POOL_FROM = 1 << 17;     // 128K words = 1 MB: from here on wordsum_full shares the array among host threads
+unsigned long long wordsum_full(const void *words, sdm_int n);       // every word (its host time is kept: wordsum_host_time)
+unsigned long long wordsum_sampled(const void *words, sdm_int n);    // 512 evenly spaced words + first and last
+unsigned long long wordsum_copy(void *dst, const void *src, sdm_int n);   // dst = src and wordsum_full(src) in one pass, on the calling thread, untimed
+void wordsum_device(sdm_plan *p, const double *v, sdm_int n);        // wordsum_full of n device words, queued on the plan's stream ...
+unsigned long long wordsum_device_result(sdm_int n);                 // ... and its value once that stream has been drained
+void wordsum_set_threads(int n);
+void wordsum_host_time(sdm_int *ns, sdm_int *calls);
+void wordsum_shutdown();                                             // joins the helper threads, frees the device and pinned words, zeroes the time
 // sdm_ada_build.hip
 void ada_build(sdm_plan *P, sdm_int N, sdm_int m, const sdm_int *Ajc, const sdm_int *Air, const double *Apr, const sdm_int *Ajc_psd, sdm_int lpN,
                sdm_int lorN, sdm_int sdpN, sdm_int rsdpN, const sdm_int *sdpNL, const sdm_int *qblkstart, const sdm_int *psd_blkstart,

@@ -17,13 +17,11 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
   if ((sdm_int)numel(qp) != m) mexErrMsgTxt("Aord.qperm size mismatch");
   IdxView Qjc = jc_of(Q), Qir = ir_of(Q);
   ivec qperm = idx_from_dbl(qp, -1);
-  const double tin = lazy_token_of(ADA);                             // (lazy intermediates: token in -> token out)
-  IdxView jc, ir;
-  if (tin == 0.0) { jc = jc_of(ADA); ir = ir_of(ADA); }
+  const AdaOrToken X(ADA);                                           // (lazy intermediates: token in -> token out)
   const bool lazy = sdm_mexcache_lazy() >= 1 && m >= 2;           // (a 1 x 1 token would be indistinguishable from a genuine 1 x 1 ADA')
   double tout = 0.0;
-  if (!lazy) plhs[0] = tin == 0.0 ? sparse_like(ADA) : sparse_of_token(tin, m);   // getada2.c:153 (the values come back from the device)
-  sdm_check(sdm_mexcache_getada2(m, tin == 0.0 ? jc.data() : NULL, tin == 0.0 ? ir.data() : NULL, tin == 0.0 ? mxGetPr(ADA) : NULL, lazy ? NULL : mxGetPr(plhs[0]),
-                                 ck.K.lorN, Qjc.data(), Qir.data(), mxGetPr(Q), qperm.data(), tin, lazy ? &tout : NULL));
+  plhs[0] = X.output(lazy, m);                                      // getada2.c:153 (the values come back from the device)
+  sdm_check(sdm_mexcache_getada2(m, X.jc(), X.ir(), X.pr(), lazy ? NULL : mxGetPr(plhs[0]), ck.K.lorN, Qjc.data(), Qir.data(), mxGetPr(Q), qperm.data(),
+                                 X.token, lazy ? &tout : NULL));
   if (lazy) plhs[0] = make_token(m, tout);
 }

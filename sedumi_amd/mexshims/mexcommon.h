@@ -92,6 +92,18 @@ inline mxArray *sparse_of_token(double tok, sdm_int m) {
   }
   return a;
 }
+// the ADA' a gateway is handed: a sparse array, or the token of one (then the cache knows the pattern and the device has the values: no arrays)
+struct AdaOrToken {
+  const mxArray *a;
+  double token;
+  IdxView jcv, irv;
+  explicit AdaOrToken(const mxArray *src) : a(src), token(lazy_token_of(src)) { if (token == 0.0) { jcv = jc_of(src); irv = ir_of(src); } }
+  const sdm_int *jc() const { return token == 0.0 ? jcv.data() : NULL; }
+  const sdm_int *ir() const { return token == 0.0 ? irv.data() : NULL; }
+  const double *pr() const { return token == 0.0 ? mxGetPr(a) : NULL; }
+  // the array a gateway returns for it, values to be filled in: its pattern -- or nothing (NULL) where a token goes out instead
+  mxArray *output(bool token_out, sdm_int m) const { return token_out ? NULL : token == 0.0 ? sparse_like(a) : sparse_of_token(token, m); }
+};
 
 struct SymbL {                       // L.{L,perm,xsuper} as the numeric gateways read it (blkchol.c:266-286)
   sdm_int m, nsuper;
