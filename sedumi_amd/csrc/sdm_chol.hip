@@ -838,6 +838,7 @@ __device__ SDM_NOINLINE void front_rows_diag(SDM_GP(double) Fs_, SDM_GP(const do
 // probe of a later diagonal block waits for them).  The emulator runs workgroups one after the other: there the host
 // loops over (step, phase 1 = D, 2 = R, 3 = U) and nothing is carried in LDS.
 // (scalar arguments: they travel in the 32 argument registers of the convention; a FrontTab by reference made the kernel keep its copy in scratch)
+static_assert(FOLLOW_DT_SENTINEL == DT_SENTINEL, "the follower polls the words of DT for the sentinel the factor arms them with");
 __device__ SDM_NOINLINE void front_follow_stage(char *smem, int bx, int fs, int ns, int ld, int sld, int slot, int sboff, int64_t foff, int64_t soff, int64_t toff,
                                                  SDM_GP(const double) F_, SDM_GP(const double) DT_, SDM_GP(double) S_, SDM_GP(double) STr_, SDM_GP(int) front_cnt_,
                                                  SDM_GP(const int) diag_cnt_, SDM_GP(unsigned long long) sb_g_, SDM_GP(int) tmo_) {

@@ -258,9 +258,12 @@ __device__ __forceinline__ void prep_done(int *cnt) {
 // (sdm_chol.hip) whose columns are one super-block.  Run by the LAST workgroups of that launch (until round 4: by a launch of its
 // own on a second stream -- fork and join cost 18 us per factorisation), it follows the factor's progress counters and builds
 // X = inv(L) by block rows of 64:
-//   X(r, r) = inv(L(r, r))                                  as soon as panel r's diagonal block is published (diag_cnt),
-//   X(r, c) = - X(r, r) sum_{q = c}^{r-1} L(r, q) X(q, c)   the sum as the rows L(r, q) are published (row_cnt) and the
-//                                                            tiles X(q, c) arrive (xcnt), the product once X(r, r) is there,
+//   L(r, r) X(r, r) = I
+//   L(r, r) X(r, c) = - sum_{q = c}^{r-1} L(r, q) X(q, c)   the sum as the rows L(r, q) are published (row_cnt) and the tiles X(q, c)
+//                                                            arrive (xcnt); both systems are solved 16 columns of L(r, r) at a time as
+//                                                            panel r's diagonal block is published (follow_trisolve above),
+// (until profiles/r19a X(r, r) was the explicit inverse, built from the whole block behind diag_cnt, and X(r, c) a product with it behind its
+// counter: three dependent counter hand-overs behind the factor's last pivot; now the last group's arrival, a 16-row triangle and a store)
 // one workgroup per 64x64 tile (diagonal tiles first, then the tiles row by row: a workgroup only waits for lower ones --
 // or for the factorisation).  The factor chain takes ~20 us per panel; a tile needs one 64^3 product per panel, so the
 // inverse is complete a few microseconds after the factor instead of a chain of six dependent tile stages later (146 us
@@ -272,6 +275,112 @@ __device__ __forceinline__ void follow_wait(const int *cnt, int target, int *tmo
     for (long it = 0; sdm_signal_load(cnt) < target; it++) { if (sdm_spin_giveup(it, tmo)) break; SDM_SPIN_PAUSE(); }
   }
   __syncthreads();
+}
+// ---- L(r, r) X = B for one 64x64 tile, 16 columns of L(r, r) at a time AS THE FACTOR PUBLISHES THEM.  k_ldl_front's diagonal workgroup
+// stores its block into DT in groups of 16 columns, write-through and data-tagged (publish_group, sdm_chol_dev.h: DT starts every
+// factorisation filled with a sentinel that no computation produces; any other word is final -- also in a block that goes through the
+// general path, which publishes nothing more until its epilogue stores the whole block, the groups already out being what it computes
+// again).  The row workgroups of the chain read the groups that way; so does this routine, which needs neither the block's counter
+// nor its explicit inverse: when group g is there, rows 16 g .. 16 g + 15 of X are substituted (unit diagonal: the diagonal slots of DT
+// carry the pivots and are not read; a skipped pivot's column is zero below the diagonal) and pushed into the rows below by one K = 16
+// step per 16x16 tile on the matrix cores.  After the block's last group only a 16-row triangle is left.
+//   Bs[row*TP + col]: B on entry, X on return (rows < nb);  As: scratch, As[k*TP + i] = L(i, k), i > k, as the groups arrive.
+//   Wavefront w owns columns 16 w .. 16 w + 15 of B throughout: between a group's triangle and its update there is no workgroup barrier.
+//   identity: B = I -- X = inv(L(r, r)), lower triangular: wavefront w has nothing to do before group w.
+// Polling: ONE lane of the workgroup polls ONE word of the group (the last row's; more pollers on a block's lines have slowed the
+// factor's chain before), pausing between polls; only then is the group fetched -- every load of a work-item in flight
+// before the first is looked at -- and EVERY needed word checked against the sentinel (the rows of a group are stored by 64 lanes
+// in eight 16-byte pieces each, which arrive in no particular order).  Every wait is bounded (sdm_spin_giveup).
+// Arithmetic: the triangle's terms are explicit fma() calls (one rounding each, as on the matrix cores) and contraction is off, so that no
+// compiler decides the rounding: the device and the emulator agree.
+// Returns max |L(i, k)| over the words it fetched.
+constexpr unsigned long long FOLLOW_DT_SENTINEL = 0x7ff8dead5ed00001ull;   // = DT_SENTINEL of sdm_chol_dev.h (sdm_chol.hip asserts it)
+__device__ __forceinline__ bool follow_is_sentinel(double v) { return double_to_bits(v) == FOLLOW_DT_SENTINEL; }
+constexpr int FGW = NB * 16 / ST;   // words of a group per work-item
+__device__ __forceinline__ double follow_group_fetch(const double *Ds, int g, int nb, double *As, int *tmo) {
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    const double *a = &Ds[(nb - 1) * NB + min(16 * g + 15, nb - 1)];   // (the last group's is a diagonal slot: the pivot travels there)
+    double v = sdm_load_wt(a);
+    for (long it = 0; follow_is_sentinel(v); it++) { if (sdm_spin_giveup(it, tmo)) break; SDM_SPIN_PAUSE(); v = sdm_load_wt(a); }
+  }
+  __syncthreads();
+  double v[FGW];
+#pragma unroll
+  for (int t = 0; t < FGW; t++) {
+    const int e = tid + ST * t, i = e >> 4, j = 16 * g + (e & 15);
+    v[t] = (i < nb && j < i) ? sdm_load_wt(&Ds[i * NB + j]) : 0.0;
+  }
+  // (one loop for the work-item's words: whichever is still the sentinel is read again)
+  for (long it = 0;; it++) {
+    bool late = false;
+#pragma unroll
+    for (int t = 0; t < FGW; t++) late = late || follow_is_sentinel(v[t]);
+    if (!late || sdm_spin_giveup(it, tmo)) break;
+    SDM_SPIN_PAUSE();
+#pragma unroll
+    for (int t = 0; t < FGW; t++) {
+      const int e = tid + ST * t, i = e >> 4, j = 16 * g + (e & 15);
+      if (follow_is_sentinel(v[t])) v[t] = sdm_load_wt(&Ds[i * NB + j]);
+    }
+  }
+  double mx = 0.0;
+#pragma unroll
+  for (int t = 0; t < FGW; t++) {
+    const int e = tid + ST * t, i = e >> 4, j = 16 * g + (e & 15);
+    As[j * TP + i] = v[t];
+    mx = fmax(mx, fabs(v[t]));
+  }
+  __syncthreads();
+  return mx;
+}
+__device__ __forceinline__ double follow_trisolve(double *As, double *Bs, const double *Ds, int nb_, bool identity, int wave_, int lane, int *tmo) {
+  SDM_FP_STRICT;
+  const int nb = SDM_UNIFORM_INT(nb_), wave = SDM_UNIFORM_INT(wave_);   // (the loops below are steered from scalar registers: see sinv_follow_body)
+  const int li = lane & 15, lk = lane >> 4, col = 16 * wave + li;
+  double lmx = 0.0;
+  for (int g = 0; 16 * g < nb; g++) {
+    lmx = fmax(lmx, follow_group_fetch(Ds, g, nb, As, tmo));
+    if (identity && g < wave) continue;                              // (wave-uniform) rows above the diagonal of inv(L): zero
+    double *Bg = Bs + 16 * g * TP + col;                             // Bg[i*TP] = B(16 g + i, col)
+    const double *Lg = As + 16 * g * TP + 16 * g;                    // Lg[k*TP + i] = L(16 g + i, 16 g + k)
+    if (lane < 16) {
+      // triangle of the group's 16 rows, lane = column, column by column of L: x_i -= l_ik x_k for i > k, k ascending
+      double x[16];
+#pragma unroll
+      for (int i = 0; i < 16; i++) x[i] = Bg[i * TP];
+#pragma unroll
+      for (int k = 0; k < 15; k++) {
+        // (the coefficients of column k are fetched while column k-1 is applied, not all 120 at the top)
+        const int z = k >= 1 ? SDM_ZERO_AFTER(x[k - 1]) : 0;
+        double l[16];
+#pragma unroll
+        for (int i = k + 1; i < 16; i++) l[i] = Lg[k * TP + i + z];
+#pragma unroll
+        for (int i = k + 1; i < 16; i++) x[i] = fma(-l[i], x[k], x[i]);   // (an explicit fma: one rounding per term, on the device and in the emulator alike)
+      }
+#pragma unroll
+      for (int i = 0; i < 16; i++) Bg[i * TP] = x[i];
+    }
+    SDM_WAVE_SYNC();
+    // rank-16 update of the rows below: B(t) -= L(t, g) X(g) per 16-row tile t > g, four K = 4 steps each
+    for (int t = g + 1; 16 * t < nb; t++) {
+      double *Bt = Bs + (16 * t + lk) * TP + col;                    // accumulator layout: Bt[4 r * TP] = B(16 t + lk + 4 r, col)
+      sdm_double4 acc;
+#pragma unroll
+      for (int r = 0; r < 4; r++) acc[r] = Bt[4 * r * TP];
+#pragma unroll
+      for (int s4 = 0; s4 < 4; s4++) {
+        const int k = 4 * s4 + lk;
+        acc = SDM_MFMA_F64_16x16x4(Lg[k * TP + 16 * (t - g) + li], -Bg[k * TP], acc);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) Bt[4 * r * TP] = acc[r];
+    }
+    SDM_WAVE_SYNC();
+  }
+  __syncthreads();
+  return lmx;
 }
 // the front a follower workgroup works on: scalars only, so that a called stage can take them in registers (sdm_chol.hip)
 struct FollowDesc { int ns, ld, sld, slot, sboff, s; int64_t foff, soff, toff; };
@@ -287,9 +396,12 @@ __device__ __forceinline__ FollowDesc follow_desc(const FrontTab &tab, const int
 __device__ __forceinline__ void sinv_follow_body(char *smem, int bx, const FollowDesc &fd, const double *F, const double *DT, double *S, double *STr,
                                                  int *front_cnt, const int *diag_cnt, unsigned long long *sb_g, int *tmo) {
   const int s = fd.s;
-  const int ns = fd.ns, ld = fd.ld, sld = fd.sld;
+  // (scalar registers for what steers the loops: in the called stage of k_ldl_front the front's sizes arrive in vector registers, and every
+  // loop over them would keep a lane mask in scalar registers -- the stage then runs out of them and parks its return address through scratch,
+  // which tests/test_abi.py forbids)
+  const int ns = SDM_UNIFORM_INT(fd.ns), ld = fd.ld, sld = fd.sld;
   const int T = (ns + 63) / 64;
-  const int b = bx;
+  const int b = SDM_UNIFORM_INT(bx);
   if (b >= T * (T + 1) / 2) return;
   const double *Fs = F + fd.foff;
   double *Ss = S + fd.soff, *Ts = STr + fd.soff;
@@ -300,38 +412,28 @@ __device__ __forceinline__ void sinv_follow_body(char *smem, int bx, const Follo
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (b < T) {
     // ---- diagonal tile r: inv(L(r, r)) from the transposed copy DT of the factored block
+    // (L(r, r) X = I by 16-column groups as the factor publishes them, follow_trisolve: nobody waits for this tile but the solves)
     const int r = b, nb = min(64, ns - 64 * r);
-    double *bufA = (double *)smem, *rawA = bufA + 64 * TP;          // (TILE_LDS: the two arrays of the tile role)
+    double *rawA = (double *)smem, *bufA = rawA + 64 * TP;          // (TILE_LDS: the two arrays of the tile role)
     const double *Ds = DT + fd.toff + (int64_t)r * NB * NB;      // Ds[i*NB + k] = L(64r + i, 64r + k)
-    follow_wait(diag_cnt + s, 4 * (r + 1), tmo);
-    double lmx = 0.0;
-    {
-      double va[SPT];
-      const int i = tid & 63, kq = tid >> 6;
-#pragma unroll
-      for (int j = 0; j < SPT; j++) va[j] = sdm_load_wt(&Ds[min(i, nb - 1) * NB + min(kq + (ST / 64) * j, nb - 1)]);
-#pragma unroll
-      for (int j = 0; j < SPT; j++) {
-        const int k = kq + (ST / 64) * j;
-        const double a = (i > k && i < nb) ? va[j] : 0.0;
-        rawA[k * TP + i] = a;
-        bufA[k * TP + i] = 0.0;
-        lmx = fmax(lmx, fabs(a));
-      }
-    }
+    // off the lines of DT until the block before this one is out (its counter, polled as before): block r is published after that
+    if (r > 0) follow_wait(diag_cnt + s, 4 * r, tmo);
+    for (int e = tid; e < 64 * 64; e += ST) bufA[(e >> 6) * TP + (e & 63)] = (e >> 6) == (e & 63) ? 1.0 : 0.0;
     __syncthreads();
-    inv64_pair<true>(rawA, nullptr, bufA, nullptr, wave, lane, gP);
-    __syncthreads();
+    const double lmx = follow_trisolve(rawA, bufA, Ds, nb, true, wave, lane, tmo);
     wave_atomic_max(gP + 1, lmx, lane);
+    double gm = 0.0;
     for (int e = tid; e < 64 * 64; e += ST) {
       const int i = e & 63, j = e >> 6;
-      if (i >= j && i < nb) sdm_store_wt(&Ss[(int64_t)(64 * r + j) * sld + 64 * r + i], bufA[i * TP + j]);
+      if (i >= j && i < nb) { const double v = bufA[i * TP + j]; gm = fmax(gm, fabs(v)); sdm_store_wt(&Ss[(int64_t)(64 * r + j) * sld + 64 * r + i], v); }
     }
+    wave_atomic_max(gP, gm, lane);
     for (int e = tid; e < 64 * 64; e += ST) {
       const int j = e & 63, i = e >> 6;
       if (i >= j && i < nb) Ts[(int64_t)(64 * r + i) * sld + 64 * r + j] = bufA[i * TP + j];       // (the transposed copy is read by the solves only: plain stores)
     }
     prep_done(xcnt + r * FRONT_MAXT + r);
+    SDM_TRACE(16 * r + 9);                                           // follower: X(r, r) counted
     return;
   }
   // ---- tile (r, c), c < r
@@ -355,20 +457,16 @@ __device__ __forceinline__ void sinv_follow_body(char *smem, int bx, const Follo
     __syncthreads();
   }
   wave_atomic_max(gP + 1, lmx, lane);
-  follow_wait(xcnt + r * FRONT_MAXT + r, 1, tmo);                    // X(r, r)
-  stage_colmajor_load<true>(va, Ss + (int64_t)(64 * r) * sld + 64 * r, sld, arows, arows, tid);
-  acc_to_lds_rowmajor(acc, Bs, wave, lane, 1.0);                     // the sum as a B operand: Bs[k*TP + col]
-  stage_colmajor_store(As, va, arows, arows, tid);
+  // L(r, r) X(r, c) = -sum against the block's 16-column groups as they are published: no wait for X(r, r), no product with it.  (Only
+  // now, with its sum complete, does the workgroup look at DT.)
+  acc_to_lds_rowmajor(acc, Bs, wave, lane, -1.0);                    // B = -sum: Bs[row*TP + col]
   __syncthreads();
-  acc_zero(acc);
-  mma_block(acc, As, Bs, wave, lane);
-  __syncthreads();
-  acc_to_lds_rowmajor(acc, As, wave, lane, -1.0);
-  __syncthreads();
-  const double gm = store_tile<true>(Ss + (int64_t)(64 * c) * sld + 64 * r, sld, As, arows, 64, tid);
-  store_tile_T<false>(Ts + (int64_t)(64 * r) * sld + 64 * c, sld, As, arows, 64, tid);
+  follow_trisolve(As, Bs, DT + fd.toff + (int64_t)r * NB * NB, arows, false, wave, lane, tmo);
+  const double gm = store_tile<true>(Ss + (int64_t)(64 * c) * sld + 64 * r, sld, Bs, arows, 64, tid);
+  store_tile_T<false>(Ts + (int64_t)(64 * r) * sld + 64 * c, sld, Bs, arows, 64, tid);
   wave_atomic_max(gP, gm, lane);
   prep_done(xcnt + r * FRONT_MAXT + c);
+  if (c == 0 || c == r - 1) SDM_TRACE(16 * r + (c == 0 ? 10 : 11));  // follower: X(r, 0) / X(r, r-1) counted
 }
 
 }  // namespace sdm

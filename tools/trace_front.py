@@ -36,3 +36,13 @@ for q in range(npan):
     r = t[q] - t0
     print("  q=%2d  %7.2f  %7.2f | %7.2f %7.2f %7.2f %7.2f | %7.2f  %7.2f   sweeps %.2f, end->last group %.2f, ->tile %.2f, ->acks %.2f, ->next D %.2f" % (
         q, r[0], r[1], r[2], r[3], r[4], r[5], r[7], r[8], r[1] - r[0], r[5] - r[1], r[7] - r[5], r[8] - r[7], (t[q + 1, 0] - t[q, 8]) if q + 1 < npan else 0))
+# the chain per panel (D start to D start), and the follower behind it (sdm_follow.h: slots 9 .. 11 of a tile row): when X(q, q), X(q, 0) and
+# X(q, q-1) were counted, against the end of block q's sweeps
+if npan > 1:
+    steps = np.diff(t[:npan, 0])
+    print("chain per panel (D start -> next D start): " + " ".join("%.2f" % s for s in steps) + " | mean of panels 0..%d: %.2f us" % (min(npan - 2, 9), steps[:10].mean()))
+if t[0, 9] > 0:
+    for q in range(npan):
+        r = t[q] - t[q, 1]
+        print("  follower q=%2d  us behind the end of D(q)'s sweeps: X(q,q) %7.2f" % (q, r[9]) + ("  X(q,0) %7.2f" % r[10] if q > 0 else "") + ("  X(q,q-1) %7.2f" % r[11] if q > 1 else ""))
+    print("tail: the last tile of the inverse is counted %.2f us behind the end of the last D's sweeps" % (t[npan - 1, 9:(12 if npan > 2 else 11 if npan > 1 else 10)].max() - t[npan - 1, 1]))
