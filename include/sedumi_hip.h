@@ -271,6 +271,42 @@ int sdm_qrk(const sdm_cone *K, const double *x, int frame_kind, double *q, doubl
  * Process-wide; for tests, which reach the global-memory residence at small orders. */
 int sdm_set_qr_panel_lds_budget(sdm_int bytes);
 
+/* --- next row: the re-pivoting chain of updtransfo.m:99-107 --- */
+
+/* The rotations travel in the reference's compact form, which is what a urotorder gateway hands to a givensrot gateway:
+ *   gjc  sum n_k doubles, n_k per block, whole numbers, 0-based: the rotations of step k (0 <= k < n-1) of a block are its rotations
+ *        gjc[k] .. gjc[k+1]-1, in bottom-up order, and turn rows k .. k+m, m = gjc[k+1] - gjc[k]; gjc[n-1] is the block's rotation count.
+ *   g    per rotation 2 doubles {x, y} (real block, the rotation [x, y; y, -x]) or 3 doubles {x, xim, y} (Hermitian block,
+ *        [conj(x), y; y, -x], y real), the blocks behind each other in K.s order: block k starts where the rotations of the blocks
+ *        before it end. */
+
+/* [u_out, perm_out, gjc, g] = urotorder(u, K, maxu, perm_in)     rotorder / prpirotorder, urotorder.c:79-180, :197-304, gateway :312-490
+ * Per PSD block: columns of triu(u) are re-pivoted wherever max_j |u(k, j)|^2 > maxu^2 d_k (d_k = the squared norm of column k from
+ * row k down), the pivot being the later column with the largest d (the first such position among equal ones), by Givens rotations
+ * G with  (G triu(u))(:, p) = triu(u_out).  u, u_out: lenud doubles (Hermitian blocks [Re; Im]).  ONLY THE UPPER TRIANGLE of u in the
+ * incoming column order is read (and of a Hermitian diagonal only the real part); the reference ignores the rest as well.  u_out is
+ * exactly symmetric / Hermitian with Im diag = 0 (triu2sym / triu2herm).  perm_in: NULL, or sum n_k 1-based doubles; perm_out =
+ * perm_in(p), or 1 + p when perm_in is NULL (:405-412).  gjc: sum n_k doubles.  g: the reference's capacity, 2 sum n(n-1)/2 doubles over
+ * the real blocks + 3 sum n(n-1)/2 over the Hermitian ones (may be NULL when that is 0); *g_len = the doubles used, nothing is written
+ * beyond them.  One workgroup per block in one launch; a block's bits depend on nothing but the block.  No PSD blocks: *g_len = 0. */
+int sdm_urotorder(const sdm_cone *K, const double *u, double maxu, const double *perm_in, double *u_out, double *perm_out,
+                  double *gjc, double *g, sdm_int *g_len);
+
+/* y = givensrot(gjc, g, x, K)     Y_k = G_k X_k, matgivens / prpimatgivens givensrot.c:60-84 (auxgivens.c:43-99).
+ * x, y: lenud doubles (may be the same array); gjc, g as above, g_len = the doubles of g.  Refused before anything is allocated:
+ * gjc that decreases or gives step k more than n-1-k rotations, and a g shorter than gjc says ("g size mismatch", givensrot.c:146, :156). */
+int sdm_givensrot(const sdm_cone *K, const double *gjc, const double *g, sdm_int g_len, const double *x, double *y);
+
+/* y = sqrtinv(q, vlab, K)         y(i, j) = conj(q(j, i)) / sqrt(v_i) per PSD block, sqrtinv.c:58-86.
+ * q, y: lenud doubles; vlab: K.l + 2 length(K.q) + sum(K.s) doubles as the reference requires (:120; the PSD part is taken), or
+ * sum(K.s); anything else: "v size mismatch". */
+int sdm_sqrtinv(const sdm_cone *K, const double *q, const double *vlab, sdm_int vlab_len, double *y);
+
+/* LDS bytes urotorder's working copy of a block (n x (n|1) doubles per plane) and a 64-column strip of givensrot (n x 65 doubles per
+ * plane) may take, 0 = default (98304, also the maximum).  What does not fit lives in global memory, with the same bits.
+ * Process-wide; for tests, which reach the global-memory residence at small orders. */
+int sdm_set_rot_lds_budget(sdm_int bytes);
+
 /* ================================================================ tier (2) */
 typedef struct sdm_plan sdm_plan;
 

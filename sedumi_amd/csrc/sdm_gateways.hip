@@ -284,18 +284,22 @@ static void h2d(double *d, const double *h, int64_t n) { SDM_HIP_CHECK(hipMemcpy
 static void d2h(double *h, const double *d, int64_t n) { SDM_HIP_CHECK(hipMemcpy(h, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost)); }
 // How every frame / qrK call begins and ends.  K and frame_kind are checked and the orders of K's blocks are in ns; without PSD blocks there is
 // nothing to do (p stays null: the caller returns); else no argument may be missing and the call has a plan on the thread's stream, p.
+// the checks of K and frame_kind; ns = the orders of K's blocks; false: no PSD block has an entry
+static bool frame_checks(const sdm_cone *K, int frame_kind, std::vector<int> &ns) {
+  if (!K) throw std::runtime_error("K is null");
+  if (frame_kind != SDM_FRAME_HOUSEHOLDER && frame_kind != SDM_FRAME_EXPLICIT)
+    throw std::runtime_error("frame_kind must be SDM_FRAME_HOUSEHOLDER (0) or SDM_FRAME_EXPLICIT (1)");
+  if (K->sdpN < 0 || K->rsdpN < 0 || K->rsdpN > K->sdpN) throw std::runtime_error("K: 0 <= rsdpN <= length(K.s) expected");
+  sdm_int lenud, plen;
+  cone_blocks(K, ns, lenud, plen);
+  for (int n : ns) if (n < 0) throw std::runtime_error("K.s: negative order");
+  return !std::all_of(ns.begin(), ns.end(), [](int n) { return n == 0; });
+}
 struct FrameCall {
   std::vector<int> ns;
   sdm_plan *p = nullptr;
   FrameCall(const char *who, const sdm_cone *K, int frame_kind, bool args_given) {
-    if (!K) throw std::runtime_error("K is null");
-    if (frame_kind != SDM_FRAME_HOUSEHOLDER && frame_kind != SDM_FRAME_EXPLICIT)
-      throw std::runtime_error("frame_kind must be SDM_FRAME_HOUSEHOLDER (0) or SDM_FRAME_EXPLICIT (1)");
-    if (K->sdpN < 0 || K->rsdpN < 0 || K->rsdpN > K->sdpN) throw std::runtime_error("K: 0 <= rsdpN <= length(K.s) expected");
-    sdm_int lenud, plen;
-    cone_blocks(K, ns, lenud, plen);
-    for (int n : ns) if (n < 0) throw std::runtime_error("K.s: negative order");
-    if (std::all_of(ns.begin(), ns.end(), [](int n) { return n == 0; })) return;
+    if (!frame_checks(K, frame_kind, ns)) return;
     if (!args_given) throw std::runtime_error(std::string(who) + ": null argument");
     p = sdm_plan_create(0, frame_stream());
     if (!p) plan_ok(1);
@@ -371,6 +375,90 @@ int sdm_qrk(const sdm_cone *K, const double *x, int frame_kind, double *q, doubl
   if (ex) cone_expand(C.p, T, dq, dqb);
   C.read_back(q, ex ? dqb : dq, ex ? T.lenud : T.lenfr);
   if (r) d2h(r, dr, T.lenud);
+  SDM_CATCH
+}
+// ---- urotorder, givensrot, sqrtinv (sdm_rot.hip); the call shape of the N5 / N6 entry points above
+int sdm_set_rot_lds_budget(sdm_int bytes) {
+  SDM_TRY
+  rot_set_lds_budget(bytes);
+  SDM_CATCH
+}
+int sdm_urotorder(const sdm_cone *K, const double *u, double maxu, const double *perm_in, double *u_out, double *perm_out, double *gjc, double *g,
+                  sdm_int *g_len) {
+  SDM_TRY
+  if (!g_len) throw std::runtime_error("urotorder: null argument");
+  *g_len = 0;
+  std::vector<int> ns;
+  if (!frame_checks(K, SDM_FRAME_HOUSEHOLDER, ns)) return 0;
+  if (!(maxu == maxu)) throw std::runtime_error("urotorder: maxu is not a number");
+  RotPlan S; urot_plan(S, ns, (int)K->rsdpN);
+  FrameCall C("urotorder", K, SDM_FRAME_HOUSEHOLDER, u && u_out && perm_out && gjc && (g || S.gcap == 0));
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 2, 0, 3, 2 * S.gcap + S.words());
+  double *du = T.data, *duo = du + T.lenud, *dpi = duo + T.lenud, *dpo = dpi + T.lenlab, *dgj = dpo + T.lenlab, *dgs = dgj + T.lenlab,
+         *dgo = dgs + S.gcap, *area = dgo + S.gcap;
+  h2d(du, u, T.lenud);
+  if (perm_in) h2d(dpi, perm_in, T.lenlab);
+  urot_run(C.p, T, S, area, du, duo, perm_in ? dpi : nullptr, dpo, dgj, dgs, dgo, maxu);
+  C.read_back(gjc, dgj, T.lenlab);
+  sdm_int len = 0, lo = 0;
+  for (size_t b = 0; b < ns.size(); lo += ns[b], b++)
+    if (ns[b] > 0) len += ((sdm_int)b < K->rsdpN ? 2 : 3) * (sdm_int)gjc[lo + ns[b] - 1];
+  if (len < 0 || len > S.gcap) throw std::runtime_error("urotorder: rotation count out of range");
+  d2h(perm_out, dpo, T.lenlab);
+  if (len) d2h(g, dgo, len);
+  d2h(u_out, duo, T.lenud);
+  *g_len = len;
+  SDM_CATCH
+}
+int sdm_givensrot(const sdm_cone *K, const double *gjc, const double *g, sdm_int g_len, const double *x, double *y) {
+  SDM_TRY
+  std::vector<int> ns;
+  if (!frame_checks(K, SDM_FRAME_HOUSEHOLDER, ns)) return 0;
+  if (!gjc || !x || !y || g_len < 0 || (!g && g_len > 0)) throw std::runtime_error("givensrot: null argument");
+  // gjc of every block: whole numbers that do not decrease, step k with at most n-1-k rotations (rows k .. k+m), all of them inside g
+  std::vector<int> gj32;
+  std::vector<int64_t> goff(ns.size(), 0);
+  sdm_int inz = 0, lo = 0;
+  for (size_t b = 0; b < ns.size(); lo += ns[b], b++) {
+    const int n = ns[b];
+    goff[b] = inz;
+    for (int k = 0; k < n; k++) {
+      const double v = gjc[lo + k];
+      if (!(v >= 0.0 && v <= 2147483647.0)) throw std::runtime_error("givensrot: gjc out of range");
+      gj32.push_back((int)v);
+    }
+    const int *gj = gj32.data() + lo;
+    for (int k = 0; k + 1 < n; k++)
+      if (gj[k + 1] < gj[k] || gj[k + 1] - gj[k] > n - 1 - k) throw std::runtime_error("givensrot: gjc is not a rotation count per step");
+    if (n > 0) inz += ((sdm_int)b < K->rsdpN ? 2 : 3) * (sdm_int)gj[n - 1];
+    if (inz > g_len) throw std::runtime_error("g size mismatch");       // givensrot.c:146, :156
+  }
+  RotPlan S; givens_plan(S, ns, (int)K->rsdpN, goff);
+  FrameCall C("givensrot", K, SDM_FRAME_HOUSEHOLDER, true);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 1, 0, 1, inz + S.words());
+  double *dy = T.data, *dgj = dy + T.lenud, *dg = dgj + T.lenlab, *area = dg + inz;
+  h2d(dy, x, T.lenud);
+  SDM_HIP_CHECK(hipMemcpy(dgj, gj32.data(), gj32.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (inz) h2d(dg, g, inz);
+  givens_run(C.p, T, S, area, dy, (const int *)dgj, dg);
+  C.read_back(y, dy, T.lenud);
+  SDM_CATCH
+}
+int sdm_sqrtinv(const sdm_cone *K, const double *q, const double *vlab, sdm_int vlab_len, double *y) {
+  SDM_TRY
+  std::vector<int> ns;
+  const bool work = frame_checks(K, SDM_FRAME_HOUSEHOLDER, ns);
+  sdm_int slen = 0;
+  for (int n : ns) slen += n;
+  const sdm_int skip = K->lpN + 2 * K->lorN;
+  if (vlab_len != slen && vlab_len != skip + slen) throw std::runtime_error("v size mismatch");   // sqrtinv.c:120
+  if (!work) return 0;
+  FrameCall C("sqrtinv", K, SDM_FRAME_HOUSEHOLDER, q && vlab && y);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 2, 0, 1);
+  double *dq = T.data, *dy = dq + T.lenud, *dv = dy + T.lenud;
+  h2d(dq, q, T.lenud); h2d(dv, vlab + (vlab_len == slen ? 0 : skip), T.lenlab);
+  sqrtinv_run(C.p, T, dq, dv, dy);
+  C.read_back(y, dy, T.lenud);
   SDM_CATCH
 }
 }  // extern "C"

@@ -590,4 +590,19 @@ void qrk_set_panel_lds_budget(sdm_int bytes);
 void qrk_plan(QrkSteps &S, const std::vector<int> &ns, int rsdpN);
 // q (lenfr doubles, device) and r (lenud doubles, device, holding x on entry) of every block of T; area: S.words() doubles on the device
 void qrk_run(sdm_plan *P, const ConeTabs &T, const QrkSteps &S, double *area, double *q, double *r);
+// sdm_rot.hip: urotorder, givensrot, sqrtinv in the reference's compact rotation form
+struct RotPlan {                        // host side of one urotorder / givensrot call: the image of its block offsets and work items
+  std::vector<int64_t> img;             // [offset in g per block | offset in the scratch per block | int32 items, 4 per item]
+  size_t w_items = 0, lds = 0;          // 8-byte words of img before the items; dynamic LDS of the launch
+  int nitems = 0;                       // workgroups
+  int64_t gcap = 0, ws = 0, slot = 0;   // the reference's capacity of g (doubles); doubles of scratch; of one givensrot strip in global memory
+  int64_t words() const { return ws + (int64_t)img.size(); }   // doubles the run needs in `area`
+};
+void rot_set_lds_budget(sdm_int bytes);
+void urot_plan(RotPlan &S, const std::vector<int> &ns, int rsdpN);
+void urot_run(sdm_plan *P, const ConeTabs &T, const RotPlan &S, double *area, const double *u, double *uout, const double *pin, double *pout, double *gjc,
+              double *gslot, double *gout, double maxu);
+void givens_plan(RotPlan &S, const std::vector<int> &ns, int rsdpN, const std::vector<int64_t> &goff_compact);
+void givens_run(sdm_plan *P, const ConeTabs &T, const RotPlan &S, double *area, double *y, const int *gjc, const double *g);
+void sqrtinv_run(sdm_plan *P, const ConeTabs &T, const double *q, const double *v, double *y);
 }  // namespace sdm

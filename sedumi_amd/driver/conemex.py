@@ -370,13 +370,16 @@ class NativeMex:
     """`.call(name, nlhs, *args)` like a MEX host: the cone algebra above, the hot path and the symbolic analysis through this package's library."""
     error = RuntimeError
 
-    def __init__(self, device_cone=False, device_qr=False):
+    def __init__(self, device_cone=False, device_qr=False, device_rot=False):
         """device_cone: psdframeit / psdinvjmul through the library (sedumi_amd.mex, SURVEY 8f N5) on the explicit frames this module keeps;
-        device_qr: qrK through the library too (N6), handing out the same explicit frames"""
+        device_qr: qrK through the library too (N6), handing out the same explicit frames;
+        device_rot: urotorder, givensrot and sqrtinv through the library (N7) -- gjc and g are then the reference's compact Givens form and the
+        pivots follow the reference's rule (the two forms of the rotations are opaque between urotorder and givensrot: switched together)"""
         from sedumi_amd import mex
         self._mex = mex
         self.device_cone = bool(device_cone)
         self.device_qr = bool(device_qr)
+        self.device_rot = bool(device_rot)
         self._native = {"ddot": ddot, "qblkmul": qblkmul, "vecsym": vecsym, "psdframeit": psdframeit, "psdinvjmul": psdinvjmul, "sqrtinv": sqrtinv,
                         "givensrot": givensrot, "partitA": partitA, "extractA": extractA, "findblks": findblks, "sortnnz": sortnnz}
 
@@ -386,6 +389,10 @@ class NativeMex:
             return getattr(self._mex, name)(*args, frame_kind=self._mex.FRAME_EXPLICIT)
         if self.device_qr and name == "qrK":
             return self._mex.qrK(*args, nlhs=nlhs, frame_kind=self._mex.FRAME_EXPLICIT)
+        if self.device_rot and name == "urotorder":
+            return self._mex.urotorder(*args, nlhs=nlhs)
+        if self.device_rot and name in ("givensrot", "sqrtinv"):
+            return getattr(self._mex, name)(*args)
         if name in self._native:
             return self._native[name](*args)
         if name == "qrK":

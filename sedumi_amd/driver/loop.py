@@ -490,13 +490,14 @@ class Cone:
 
 # ----------------------------------------------------------------------------------------------- the solver
 class Sedumi:
-    def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False):
+    def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False, device_rot=False):
         """(At, b, c, K) as the user passes them to sedumi.m, or -- internal=True -- already through pretransfo.m
         (the golden fixtures store the problems that way).  device_cone: the default MEX host answers psdframeit / psdinvjmul
-        through the library (NativeMex(device_cone=True)), device_qr: qrK as well (NativeMex(device_qr=True)); a host given with G keeps its own."""
-        if G is None and (device_cone or device_qr):
+        through the library (NativeMex(device_cone=True)), device_qr: qrK as well (NativeMex(device_qr=True)), device_rot: urotorder, givensrot and
+        sqrtinv (NativeMex(device_rot=True)); a host given with G keeps its own."""
+        if G is None and (device_cone or device_qr or device_rot):
             from .conemex import NativeMex
-            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr))
+            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot))
         self.G = G or gl.Glue()                                         # (default: this package's own MEX host, sedumi_amd.driver.conemex)
         self.ref = self.G.ref
         self.pars = pars or default_pars()
@@ -1181,7 +1182,7 @@ def load_mat(path):
     return At.astype(np.complex128) if np.iscomplexobj(d["c"]) else At, d["b"], d["c"], K
 
 
-def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False):
+def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False, device_rot=False):
     """sedumi(At, b, c, K) without MATLAB: the loop above on this package's library (resident plan) and its own cone algebra.
     Returns the dictionary of Sedumi.solve (x, y, cx, by, iter, feasratio, rows = the iteration log, ...)."""
-    return Sedumi(At, b, c, K, hot=hot, pars=pars, device_cone=device_cone, device_qr=device_qr).solve(verbose=verbose)
+    return Sedumi(At, b, c, K, hot=hot, pars=pars, device_cone=device_cone, device_qr=device_qr, device_rot=device_rot).solve(verbose=verbose)

@@ -647,3 +647,63 @@ def qrK(x, K, nlhs=1, frame_kind=FRAME_HOUSEHOLDER):
 def set_qr_panel_lds_budget(nbytes):
     """LDS bytes the panel of a block may take in qrK's panel step (sdm_set_qr_panel_lds_budget), 0 = default."""
     check(capi.lib().sdm_set_qr_panel_lds_budget(C.c_int64(int(nbytes))))
+
+
+# ------------------------------------------------------------- next row (SURVEY 8f N7)
+def urotorder(u, K, maxu, permIN=None, nlhs=4):
+    """[u, perm, gjc, g] = urotorder(u, K, maxu, permIN): stable re-pivoting of the triu factor by Givens rotations per PSD block
+    (urotorder.c:79-490; include/sedumi_hip.h at sdm_urotorder).  Only the upper triangle of u is read.  gjc, g: the reference's compact
+    rotation form (g is g_len x 1, 0 x 1 without a rotation); perm = permIN(p), or 1 + p without permIN.  Returns the first max(nlhs, 1) outputs."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    _, _, s, rsdpN = _Kfields(K)
+    u = f64(u)
+    if u.size != lenud:
+        raise SdmError("u size mismatch")
+    pin = None
+    if permIN is not None and np.size(permIN) > 0:
+        pin = f64(permIN)
+        if pin.size != slen:
+            raise SdmError("perm size mismatch")
+    tri = s * (s - 1) // 2
+    gcap = int(2 * np.sum(tri[:rsdpN]) + 3 * np.sum(tri[rsdpN:]))
+    uo, po, gjc = np.zeros(lenud), np.zeros(slen), np.zeros(slen)
+    g = np.zeros(max(gcap, 1))
+    glen = C.c_int64(0)
+    check(capi.lib().sdm_urotorder(C.byref(Kc), pf(u), C.c_double(float(np.asarray(maxu).ravel()[0])), pf(pin) if pin is not None else None,
+                                   pf(uo), pf(po), pf(gjc), pf(g), C.byref(glen)))
+    del keep
+    assert not g[glen.value:].any()                              # (nothing is written beyond g_len)
+    out = (uo.reshape(-1, 1), po.reshape(-1, 1), gjc.reshape(-1, 1), g[:glen.value].copy().reshape(-1, 1))
+    return out[:nlhs] if nlhs > 1 else out[0]
+
+
+def givensrot(gjc, g, x, K):
+    """y = givensrot(gjc, g, x, K): Y = G X per PSD block, gjc and g as urotorder leaves them (givensrot.c:60-168)."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    gjc, g, x = f64(gjc), f64(g), f64(x)
+    if x.size != lenud:
+        raise SdmError("x size mismatch")
+    if gjc.size != slen:
+        raise SdmError("gjc size mismatch")
+    y = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_givensrot(C.byref(Kc), pf(gjc), pf(g) if g.size else None, C.c_int64(g.size), pf(x), pf(y)))
+    del keep
+    return y.reshape(-1, 1)
+
+
+def sqrtinv(q, vlab, K):
+    """y = sqrtinv(q, vlab, K): y(i, j) = conj(q(j, i)) / sqrt(v_i) per PSD block (sqrtinv.c:58-145); vlab the whole spectral vector
+    (K.l + 2 length(K.q) + sum(K.s)) or its PSD part."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    q, vlab = f64(q), f64(vlab)
+    if q.size != lenud:
+        raise SdmError("q size mismatch")
+    y = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_sqrtinv(C.byref(Kc), pf(q), pf(vlab) if vlab.size else None, C.c_int64(vlab.size), pf(y)))
+    del keep
+    return y.reshape(-1, 1)
+
+
+def set_rot_lds_budget(nbytes):
+    """LDS bytes urotorder's working copy / givensrot's column strip may take (sdm_set_rot_lds_budget), 0 = default."""
+    check(capi.lib().sdm_set_rot_lds_budget(C.c_int64(int(nbytes))))
