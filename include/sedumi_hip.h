@@ -307,6 +307,34 @@ int sdm_sqrtinv(const sdm_cone *K, const double *q, const double *vlab, sdm_int 
  * Process-wide; for tests, which reach the global-memory residence at small orders. */
 int sdm_set_rot_lds_budget(sdm_int bytes);
 
+/* --- next row: the two ends of that chain, and the chain as one call -- */
+
+/* z = triumtriu(x, y, K)          triumtriu.m:40-71.  Per PSD block Z = triu(X) triu(Y), then the strict lower triangle of Z = the
+ * conjugate of its strict upper one (ZZ + triu(ZZ,1)').  x, y: len doubles each, of which the LAST lenud are taken (:50; a whole cone
+ * vector or its PSD part; len < lenud: "size mismatch"); z: lenud doubles.  ONLY THE UPPER TRIANGLES of x and y are read: what lies
+ * below the diagonal (urotorder and psdfactor leave a mirrored copy there) never enters the arithmetic.  The diagonal of a Hermitian
+ * block is written as computed, on both planes: its imaginary part is NOT set to 0 (the .m file does not either).
+ * 64 x 64 tiles I <= J on the FP64 matrix cores, the k loop over the tiles I .. J only; a block's bits depend on nothing but the block.
+ * No PSD blocks: returns 0, writes nothing. */
+int sdm_triumtriu(const sdm_cone *K, const double *x, const double *y, sdm_int len, double *z);
+
+/* The PSD part of updtransfo.m:99-108 as one call, every input uploaded once and every step on the device:
+ *     du                  = triumtriu(ux, u_in, K)
+ *     [du, perm, gjc, g]  = urotorder(du, K, maxu, perm_in)
+ *     q                   = givensrot(gjc, g, q, K)
+ *     vinv                = sqrtinv(q, vlab, K)
+ *     [frame, r]          = qrK(vinv, K)
+ *     u_out               = triumtriu(r, du, K)
+ * ux, u_in, q, u_out: lenud doubles; perm_in: NULL or sum(K.s) doubles, perm_out: sum(K.s) doubles (as sdm_urotorder); vlab, vlab_len as
+ * sdm_sqrtinv; maxu as sdm_urotorder; frame: lenud + hLen doubles (SDM_FRAME_HOUSEHOLDER) or lenud (SDM_FRAME_EXPLICIT), as sdm_qrk.
+ * The only transfer in the middle is gjc (sum(K.s) doubles): the host plans givensrot on it, after the checks sdm_givensrot makes; the
+ * rotations g stay where urotorder left them.  The same kernels on the same bits in the same order as the six single calls: the
+ * results are bit-equal to theirs, under every LDS budget (sdm_set_rot_lds_budget, sdm_set_qr_panel_lds_budget,
+ * sdm_set_frame_lds_budget).  No PSD blocks: returns 0, writes nothing. */
+int sdm_updtransfo_psd(const sdm_cone *K, const double *ux, const double *u_in, const double *perm_in /* may be NULL */,
+                       const double *q, const double *vlab, sdm_int vlab_len, double maxu, int frame_kind,
+                       double *u_out, double *perm_out, double *frame);
+
 /* ================================================================ tier (2) */
 typedef struct sdm_plan sdm_plan;
 

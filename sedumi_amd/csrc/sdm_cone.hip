@@ -19,6 +19,9 @@
 // k_cone_gemm<MODE>: 64 x 64 output tiles, 4 wavefronts of 2 x 2 v_mfma_f64_16x16x4_f64 tiles each (the blocking of k_psdscale), over a
 // tile list of all blocks; the operand accessors carry the transposes, conjugates, diag(lab) and the mirrored lower triangle of y.
 // Products that are Hermitian by construction form only tiles I >= J and write every entry twice, mirrored (Im diag = 0).
+//
+// k_triumtriu (row N8): Z = triu(X) triu(Y) + the conjugate mirror of its strict upper triangle (triumtriu.m:63-64), the two ends of the
+// re-pivoting chain of updtransfo.m:99-108; the same blocking on the tiles I <= J, k-tiles I .. J only (see at the kernel).
 #include "sdm_plan.h"
 #include <algorithm>
 #include <cstring>
@@ -250,6 +253,66 @@ k_cone_gemm(double *out, const double *in, const double *qb, const double *lab, 
   }
 }
 
+// ---------------------------------------------------------------- triumtriu (updtransfo.m:99, :108)
+//   ZZ = triu(X) triu(Y);  Z = ZZ + triu(ZZ, 1)^H                               triumtriu.m:63-64
+// The blocking of k_cone_gemm on the tiles I <= J only, and of the k-tiles only K = I .. J: X(r, k) = 0 for k < r and Y(k, c) = 0 for k > c, so
+// every other k-tile is zero by structure.  On the diagonal tiles (K = I for X, K = J for Y) the fetch SELECTS 0.0 below the diagonal: the
+// strict lower triangle of neither operand is read (urotorder and psdfactor leave a mirrored copy there; whatever is there stays out of the
+// arithmetic).  Every entry with row <= col is written to (row, col) and, conjugated, to (col, row); the diagonal as computed on both planes --
+// triumtriu.m does not zero its imaginary part.  A tile is formed by one workgroup on its own: no hand-over between workgroups, no counters, no
+// atomics, and a block's bits depend on nothing but the block.  Tiles are dealt longest k loop first (cone_tables).
+__global__ void __launch_bounds__(CN_T)
+k_triumtriu(double *out, const double *xin, const double *yin, ConeBlk B, const int *items) {
+  __shared__ double As[64 * CN_P], Bs[64 * CN_P];
+  const int b = items[4 * blockIdx.x], I = items[4 * blockIdx.x + 1], J = items[4 * blockIdx.x + 2];
+  const int n = B.n[b], herm = B.herm[b];
+  const int64_t nn = (int64_t)n * n;
+  const double *X = xin + B.off[b], *Y = yin + B.off[b];
+  double *O = out + B.off[b];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r0 = 64 * I, c0 = 64 * J;
+  // triu(M)(r, c): the entry for r <= c inside the block, 0.0 (not fetched) elsewhere
+  auto Uv = [&](const double *M, int r, int c, int pl) -> double { return (r <= c && c < n) ? M[(int64_t)pl * nn + (int64_t)c * n + r] : 0.0; };
+  const int nplanes = herm ? 2 : 1;
+  for (int opl = 0; opl < nplanes; opl++) {
+    ConeAcc acc;
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc.t[i][j][r] = 0.0;
+    // Z = X Y on planes: Zre = Xre Yre - Xim Yim ; Zim = Xre Yim + Xim Yre
+    for (int term = 0; term < nplanes; term++) {
+      const int apl = term, bpl = opl ^ term;
+      const bool neg = opl == 0 && term == 1;
+      for (int kb = r0; kb <= c0; kb += 64) {
+        __syncthreads();
+        for (int e = tid; e < 64 * 64; e += CN_T) {
+          const int f = e & 63, s = e >> 6;                           // As[k][row]: row fastest; Bs[k][col]: k fastest (as stored)
+          { const double v = Uv(X, r0 + f, kb + s, apl); As[s * CN_P + f] = neg ? -v : v; }
+          Bs[f * CN_P + s] = Uv(Y, kb + f, c0 + s, bpl);
+        }
+        __syncthreads();
+        cone_mma(acc, As, Bs, wave, lane);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int row = r0 + 32 * (wave & 1) + 16 * i + (lane >> 4) + 4 * r, col = c0 + 32 * (wave >> 1) + 16 * j + (lane & 15);
+          if (row <= col && col < n) {
+            const double v = acc.t[i][j][r];
+            O[(int64_t)opl * nn + (int64_t)col * n + row] = v;
+            if (row != col) O[(int64_t)opl * nn + (int64_t)row * n + col] = opl ? -v : v;
+          }
+        }
+  }
+}
+
 // =========================================================================== host
 void cone_set_frame_lds_budget(sdm_int bytes) {
   if (bytes < 0 || bytes > FX_LDS_DEFAULT) throw std::runtime_error("frame LDS budget: 0 (default) .. 65536 bytes");
@@ -263,6 +326,8 @@ void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, i
   std::vector<int64_t> bo(std::max(nb, 1), 0), bf(std::max(nb, 1), 0);
   struct Strip { int b, j0, w, lds; double cost; };
   std::vector<Strip> st;
+  struct Tile { int b, I, J, cost; };
+  std::vector<Tile> ut;
   int64_t o = 0, fo = 0; int lo = 0;
   T.lds = 0;
   for (int k = 0; k < nb; k++) {
@@ -275,6 +340,7 @@ void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, i
       for (int J = 0; J < nt; J++) {
         full.insert(full.end(), {k, I, J, 0});
         if (I >= J) low.insert(low.end(), {k, I, J, 0});
+        if (I <= J) ut.push_back({k, I, J, (J - I + 1) * planes * planes});   // k-tiles I .. J, on every pair of planes
       }
     // strip width from the LDS budget: as many columns as fit, a multiple of the wavefronts, FX_WMAX at most; fewer than FX_WMIN: in global memory
     const int64_t colbytes = (int64_t)planes * std::max(n, 1) * (int64_t)sizeof(double);
@@ -290,14 +356,19 @@ void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, i
   std::stable_sort(st.begin(), st.end(), [](const Strip &a, const Strip &b) { return a.cost > b.cost; });   // longest first
   std::vector<int> strips;
   for (const Strip &s : st) strips.insert(strips.end(), {s.b, s.j0, s.w, s.lds});
-  T.nfull = (int)full.size() / 4; T.nlow = (int)low.size() / 4; T.nstrips = (int)strips.size() / 4;
+  std::stable_sort(ut.begin(), ut.end(), [](const Tile &a, const Tile &b) { return a.cost > b.cost; });     // longest first
+  std::vector<int> up;
+  for (const Tile &t : ut) up.insert(up.end(), {t.b, t.I, t.J, 0});
+  T.nfull = (int)full.size() / 4; T.nlow = (int)low.size() / 4; T.nstrips = (int)strips.size() / 4; T.nup = (int)up.size() / 4;
   if (full.empty()) full.assign(4, 0);
   if (low.empty()) low.assign(4, 0);
   if (strips.empty()) strips.assign(4, 0);
-  // one allocation, one copy: [off, foff | n, herm, loff, tiles, tiles I >= J, strips (int32, padded to 8 bytes) | the caller's doubles]
+  if (up.empty()) up.assign(4, 0);
+  // one allocation, one copy: [off, foff | n, herm, loff, tiles, tiles I >= J, strips, tiles I <= J (int32, padded to 8 bytes) | the caller's doubles]
   std::vector<int> ints;
-  const size_t o_n = 0, o_h = o_n + bn.size(), o_l = o_h + bh.size(), o_f = o_l + bl.size(), o_w = o_f + full.size(), o_s = o_w + low.size();
-  for (const std::vector<int> *v : {&bn, &bh, &bl, &full, &low, &strips}) ints.insert(ints.end(), v->begin(), v->end());
+  const size_t o_n = 0, o_h = o_n + bn.size(), o_l = o_h + bh.size(), o_f = o_l + bl.size(), o_w = o_f + full.size(), o_s = o_w + low.size(),
+               o_u = o_s + strips.size();
+  for (const std::vector<int> *v : {&bn, &bh, &bl, &full, &low, &strips, &up}) ints.insert(ints.end(), v->begin(), v->end());
   if (ints.size() & 1) ints.push_back(0);
   std::vector<int64_t> img(bo);
   img.insert(img.end(), bf.begin(), bf.end());
@@ -308,7 +379,7 @@ void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, i
   SDM_HIP_CHECK(hipMemcpy(T.arena.p, img.data(), w_dat * sizeof(int64_t), hipMemcpyHostToDevice));
   T.off = T.arena.p; T.foff = T.arena.p + bo.size();
   const int *ip = (const int *)(T.arena.p + w_int);
-  T.n = ip + o_n; T.herm = ip + o_h; T.loff = ip + o_l; T.items_full = ip + o_f; T.items_low = ip + o_w; T.strips = ip + o_s;
+  T.n = ip + o_n; T.herm = ip + o_h; T.loff = ip + o_l; T.items_full = ip + o_f; T.items_low = ip + o_w; T.strips = ip + o_s; T.items_up = ip + o_u;
   T.data = (double *)(T.arena.p + w_dat);
   T.lenud = o; T.lenfr = fo; T.lenlab = lo;
 }
@@ -335,6 +406,12 @@ void cone_invjmul(sdm_plan *P, const ConeTabs &T, const double *qb, const double
   SDM_KLAUNCH(P, k_cone_gemm<2>, dim3(T.nlow), dim3(CN_T), 0, t2, (const double *)t1, qb, xlab, B, T.items_low);
   SDM_KLAUNCH(P, k_cone_gemm<3>, dim3(T.nfull), dim3(CN_T), 0, t1, (const double *)t2, qb, xlab, B, T.items_full);
   SDM_KLAUNCH(P, k_cone_gemm<4>, dim3(T.nlow), dim3(CN_T), 0, z, (const double *)t1, qb, xlab, B, T.items_low);
+  SDM_HIP_CHECK(hipGetLastError());
+}
+// z = triu(x) triu(y) + the conjugate mirror of its strict upper triangle, per block; everything on the device, z distinct from x and y
+void cone_triumtriu(sdm_plan *P, const ConeTabs &T, const double *x, const double *y, double *z) {
+  if (T.nup == 0) return;
+  SDM_KLAUNCH(P, k_triumtriu, dim3(T.nup), dim3(CN_T), 0, z, x, y, cone_blk(T), T.items_up);
   SDM_HIP_CHECK(hipGetLastError());
 }
 

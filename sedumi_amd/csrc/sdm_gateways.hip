@@ -410,14 +410,12 @@ int sdm_urotorder(const sdm_cone *K, const double *u, double maxu, const double 
   *g_len = len;
   SDM_CATCH
 }
-int sdm_givensrot(const sdm_cone *K, const double *gjc, const double *g, sdm_int g_len, const double *x, double *y) {
-  SDM_TRY
-  std::vector<int> ns;
-  if (!frame_checks(K, SDM_FRAME_HOUSEHOLDER, ns)) return 0;
-  if (!gjc || !x || !y || g_len < 0 || (!g && g_len > 0)) throw std::runtime_error("givensrot: null argument");
-  // gjc of every block: whole numbers that do not decrease, step k with at most n-1-k rotations (rows k .. k+m), all of them inside g
-  std::vector<int> gj32;
-  std::vector<int64_t> goff(ns.size(), 0);
+// gjc of every block: whole numbers that do not decrease, step k with at most n-1-k rotations (rows k .. k+m), all of them inside the g_len doubles
+// of g.  gj32 = gjc as int32, goff = where every block's rotations begin in the compact g; returns the doubles of g they take
+static sdm_int givens_counts(const sdm_cone *K, const std::vector<int> &ns, const double *gjc, sdm_int g_len, std::vector<int> &gj32,
+                             std::vector<int64_t> &goff) {
+  gj32.clear();
+  goff.assign(ns.size(), 0);
   sdm_int inz = 0, lo = 0;
   for (size_t b = 0; b < ns.size(); lo += ns[b], b++) {
     const int n = ns[b];
@@ -433,6 +431,16 @@ int sdm_givensrot(const sdm_cone *K, const double *gjc, const double *g, sdm_int
     if (n > 0) inz += ((sdm_int)b < K->rsdpN ? 2 : 3) * (sdm_int)gj[n - 1];
     if (inz > g_len) throw std::runtime_error("g size mismatch");       // givensrot.c:146, :156
   }
+  return inz;
+}
+int sdm_givensrot(const sdm_cone *K, const double *gjc, const double *g, sdm_int g_len, const double *x, double *y) {
+  SDM_TRY
+  std::vector<int> ns;
+  if (!frame_checks(K, SDM_FRAME_HOUSEHOLDER, ns)) return 0;
+  if (!gjc || !x || !y || g_len < 0 || (!g && g_len > 0)) throw std::runtime_error("givensrot: null argument");
+  std::vector<int> gj32;
+  std::vector<int64_t> goff;
+  const sdm_int inz = givens_counts(K, ns, gjc, g_len, gj32, goff);
   RotPlan S; givens_plan(S, ns, (int)K->rsdpN, goff);
   FrameCall C("givensrot", K, SDM_FRAME_HOUSEHOLDER, true);
   ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 1, 0, 1, inz + S.words());
@@ -459,6 +467,69 @@ int sdm_sqrtinv(const sdm_cone *K, const double *q, const double *vlab, sdm_int 
   h2d(dq, q, T.lenud); h2d(dv, vlab + (vlab_len == slen ? 0 : skip), T.lenlab);
   sqrtinv_run(C.p, T, dq, dv, dy);
   C.read_back(y, dy, T.lenud);
+  SDM_CATCH
+}
+// ---- triumtriu (sdm_cone.hip), and with it the whole PSD chain of updtransfo.m:99-108 as one call
+int sdm_triumtriu(const sdm_cone *K, const double *x, const double *y, sdm_int len, double *z) {
+  SDM_TRY
+  std::vector<int> ns;
+  const bool work = frame_checks(K, SDM_FRAME_HOUSEHOLDER, ns);
+  sdm_int lenud, plen;
+  cone_blocks(K, ns, lenud, plen);
+  if (len < lenud) throw std::runtime_error("triumtriu: size mismatch");
+  if (!work) return 0;
+  FrameCall C("triumtriu", K, SDM_FRAME_HOUSEHOLDER, x && y && z);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 3, 0, 0);
+  double *dx = T.data, *dy = dx + T.lenud, *dz = dy + T.lenud;
+  h2d(dx, x + (len - lenud), T.lenud); h2d(dy, y + (len - lenud), T.lenud);    // triumtriu.m:50: the last lenud entries of both
+  cone_triumtriu(C.p, T, dx, dy, dz);
+  C.read_back(z, dz, T.lenud);
+  SDM_CATCH
+}
+int sdm_updtransfo_psd(const sdm_cone *K, const double *ux, const double *u_in, const double *perm_in, const double *q, const double *vlab,
+                       sdm_int vlab_len, double maxu, int frame_kind, double *u_out, double *perm_out, double *frame) {
+  SDM_TRY
+  std::vector<int> ns;
+  const bool work = frame_checks(K, frame_kind, ns);
+  sdm_int slen = 0;
+  for (int n : ns) slen += n;
+  const sdm_int skip = K->lpN + 2 * K->lorN;
+  if (vlab_len != slen && vlab_len != skip + slen) throw std::runtime_error("v size mismatch");   // sqrtinv.c:120
+  if (!work) return 0;
+  if (!(maxu == maxu)) throw std::runtime_error("updtransfo_psd: maxu is not a number");
+  const int rs = (int)K->rsdpN, ex = frame_kind == SDM_FRAME_EXPLICIT ? 1 : 0;
+  RotPlan SU, SG; urot_plan(SU, ns, rs);
+  givens_plan(SG, ns, rs, std::vector<int64_t>(ns.size(), 0));       // (sized here; planned again below, once gjc says where every block's rotations begin)
+  QrkSteps SQ; qrk_plan(SQ, ns, rs);
+  const int64_t wg = SG.words();
+  FrameCall C("updtransfo_psd", K, frame_kind, ux && u_in && q && vlab && u_out && perm_out && frame);
+  // six matrices: a = ux, later the result; b = u_in, later the explicit frame; c = ux u_in; d = urotorder's u; e = q, rotated in place; f = vinv, then r
+  ConeTabs T; cone_tables(T, C.ns, rs, 6, 1, 5, 2 * SU.gcap + SU.words() + wg + SQ.words());
+  double *da = T.data, *db = da + T.lenud, *dc = db + T.lenud, *dd = dc + T.lenud, *de = dd + T.lenud, *df = de + T.lenud, *dfr = df + T.lenud,
+         *dpi = dfr + T.lenfr, *dpo = dpi + T.lenlab, *dgj = dpo + T.lenlab, *dgi = dgj + T.lenlab, *dv = dgi + T.lenlab, *dgs = dv + T.lenlab,
+         *dgo = dgs + SU.gcap, *area_u = dgo + SU.gcap, *area_g = area_u + SU.words(), *area_q = area_g + wg;
+  h2d(da, ux, T.lenud); h2d(db, u_in, T.lenud); h2d(de, q, T.lenud);
+  if (perm_in) h2d(dpi, perm_in, T.lenlab);
+  h2d(dv, vlab + (vlab_len == slen ? 0 : skip), T.lenlab);
+  cone_triumtriu(C.p, T, da, db, dc);                                                                    // updtransfo.m:99
+  urot_run(C.p, T, SU, area_u, dc, dd, perm_in ? dpi : nullptr, dpo, dgj, dgs, dgo, maxu);               // :100
+  // the one transfer in the middle: gjc, which says how many rotations every step has (the host plans givensrot's strips on it)
+  std::vector<double> gjc((size_t)T.lenlab);
+  C.read_back(gjc.data(), dgj, T.lenlab);
+  std::vector<int> gj32;
+  std::vector<int64_t> goff;
+  givens_counts(K, ns, gjc.data(), SU.gcap, gj32, goff);
+  givens_plan(SG, ns, rs, goff);
+  if (SG.words() != wg) throw std::runtime_error("updtransfo_psd: givensrot's plan changed size");
+  SDM_HIP_CHECK(hipMemcpy(dgi, gj32.data(), gj32.size() * sizeof(int), hipMemcpyHostToDevice));
+  givens_run(C.p, T, SG, area_g, de, (const int *)dgi, dgo);                                             // :102, g where urotorder left it
+  sqrtinv_run(C.p, T, de, dv, df);                                                                       // :103
+  qrk_run(C.p, T, SQ, area_q, dfr, df);                                                                  // :107
+  cone_triumtriu(C.p, T, df, dd, da);                                                                    // :108
+  if (ex) cone_expand(C.p, T, dfr, db);
+  C.read_back(u_out, da, T.lenud);
+  d2h(perm_out, dpo, T.lenlab);
+  d2h(frame, ex ? db : dfr, ex ? T.lenud : T.lenfr);
   SDM_CATCH
 }
 }  // extern "C"

@@ -563,9 +563,10 @@ void psd_invcholfac(hipStream_t st, const double *u, double *y, const int *perm,
 struct ConeTabs {                       // one device allocation: the tables of a list of PSD blocks (orders / offsets, tile lists, the expansion's
   DevBuf<int64_t> arena;                //   column strips) and behind them the doubles the caller asked for (a host-pointer call: ONE hipMalloc / hipFree)
   const int *n = nullptr, *herm = nullptr, *loff = nullptr, *items_full = nullptr, *items_low = nullptr, *strips = nullptr;
+  const int *items_up = nullptr;        // the tiles I <= J of every block, longest k loop first (triumtriu)
   const int64_t *off = nullptr, *foff = nullptr;
   double *data = nullptr;               // the caller's doubles
-  int nfull = 0, nlow = 0, nstrips = 0;
+  int nfull = 0, nlow = 0, nstrips = 0, nup = 0;
   size_t lds = 0;                       // dynamic LDS of the expansion launch
   int64_t lenud = 0, lenfr = 0, lenlab = 0;   // doubles of x / Qb, of the Householder frames, of lab
 };
@@ -576,6 +577,8 @@ void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, i
 void cone_expand(sdm_plan *P, const ConeTabs &T, const double *frms, double *qb);
 void cone_frameit(sdm_plan *P, const ConeTabs &T, const double *qb, const double *lab, double *x);
 void cone_invjmul(sdm_plan *P, const ConeTabs &T, const double *qb, const double *xlab, const double *y, double *t1, double *t2, double *z);
+// z = triu(x) triu(y), mirrored, per block (triumtriu.m:63-64); x, y, z: lenud doubles on the device, z none of x, y
+void cone_triumtriu(sdm_plan *P, const ConeTabs &T, const double *x, const double *y, double *z);
 // sdm_qrk.hip: [q, r] = qrK(x, K) as a blocked Householder QR with compact-WY trailing updates
 struct QrkSteps {                       // host side of one call: the launches of every panel step and the image of their item tables
   struct Step { int j0, panel0, npanel, strip0, nstrip, tile0, ntile; size_t lds; };

@@ -370,16 +370,19 @@ class NativeMex:
     """`.call(name, nlhs, *args)` like a MEX host: the cone algebra above, the hot path and the symbolic analysis through this package's library."""
     error = RuntimeError
 
-    def __init__(self, device_cone=False, device_qr=False, device_rot=False):
+    def __init__(self, device_cone=False, device_qr=False, device_rot=False, device_updt=False):
         """device_cone: psdframeit / psdinvjmul through the library (sedumi_amd.mex, SURVEY 8f N5) on the explicit frames this module keeps;
         device_qr: qrK through the library too (N6), handing out the same explicit frames;
         device_rot: urotorder, givensrot and sqrtinv through the library (N7) -- gjc and g are then the reference's compact Givens form and the
-        pivots follow the reference's rule (the two forms of the rotations are opaque between urotorder and givensrot: switched together)"""
+        pivots follow the reference's rule (the two forms of the rotations are opaque between urotorder and givensrot: switched together);
+        device_updt: the PSD part of updtransfo.m:99-108 (triumtriu, urotorder, givensrot, sqrtinv, qrK, triumtriu) as ONE call of the library (N8),
+        "updtransfo_psd", which the driver then makes in place of those six steps -- the pivots follow the reference's rule, as with device_rot"""
         from sedumi_amd import mex
         self._mex = mex
         self.device_cone = bool(device_cone)
         self.device_qr = bool(device_qr)
         self.device_rot = bool(device_rot)
+        self.device_updt = bool(device_updt)
         self._native = {"ddot": ddot, "qblkmul": qblkmul, "vecsym": vecsym, "psdframeit": psdframeit, "psdinvjmul": psdinvjmul, "sqrtinv": sqrtinv,
                         "givensrot": givensrot, "partitA": partitA, "extractA": extractA, "findblks": findblks, "sortnnz": sortnnz}
 
@@ -389,6 +392,8 @@ class NativeMex:
             return getattr(self._mex, name)(*args, frame_kind=self._mex.FRAME_EXPLICIT)
         if self.device_qr and name == "qrK":
             return self._mex.qrK(*args, nlhs=nlhs, frame_kind=self._mex.FRAME_EXPLICIT)
+        if self.device_updt and name == "updtransfo_psd":
+            return self._mex.updtransfo_psd(*args, frame_kind=self._mex.FRAME_EXPLICIT)
         if self.device_rot and name == "urotorder":
             return self._mex.urotorder(*args, nlhs=nlhs)
         if self.device_rot and name in ("givensrot", "sqrtinv"):

@@ -490,14 +490,15 @@ class Cone:
 
 # ----------------------------------------------------------------------------------------------- the solver
 class Sedumi:
-    def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False, device_rot=False):
+    def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False):
         """(At, b, c, K) as the user passes them to sedumi.m, or -- internal=True -- already through pretransfo.m
         (the golden fixtures store the problems that way).  device_cone: the default MEX host answers psdframeit / psdinvjmul
         through the library (NativeMex(device_cone=True)), device_qr: qrK as well (NativeMex(device_qr=True)), device_rot: urotorder, givensrot and
-        sqrtinv (NativeMex(device_rot=True)); a host given with G keeps its own."""
-        if G is None and (device_cone or device_qr or device_rot):
+        sqrtinv (NativeMex(device_rot=True)), device_updt: the PSD part of updtransfo.m:99-108 as one call (NativeMex(device_updt=True));
+        a host given with G keeps its own."""
+        if G is None and (device_cone or device_qr or device_rot or device_updt):
             from .conemex import NativeMex
-            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot))
+            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot, device_updt=device_updt))
         self.G = G or gl.Glue()                                         # (default: this package's own MEX host, sedumi_amd.driver.conemex)
         self.ref = self.G.ref
         self.pars = pars or default_pars()
@@ -937,7 +938,11 @@ class Sedumi:
             tmp[tmp == 0] = 1
             psi2 = psi2 + cn.qblkmul(gamma, dIN["q2"])
             vfrm["q"] = cn.qblkmul(1 / tmp, psi2)
-        if cn.s.size:
+        if cn.s.size and getattr(ref, "device_updt", False):           # the six steps below as one call of the library, the frames explicit
+            u, perm, frs = ref.call("updtransfo_psd", 3, col(w["ux"]), col(dIN["u"]), col(dIN["perm"]) if np.size(dIN["perm"]) else None, col(q),
+                                    col(vfrm["lab"]), K, 1.1)
+            vfrm["s"] = vec(frs); d["u"] = vec(u); d["perm"] = vec(perm)
+        elif cn.s.size:
             du = cn.triumtriu(w["ux"], dIN["u"])
             args = (col(du), K, 1.1) + ((col(dIN["perm"]),) if np.size(dIN["perm"]) else ())
             du, perm, gjc, g = ref.call("urotorder", 4, *args)
@@ -1182,7 +1187,8 @@ def load_mat(path):
     return At.astype(np.complex128) if np.iscomplexobj(d["c"]) else At, d["b"], d["c"], K
 
 
-def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False, device_rot=False):
+def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False):
     """sedumi(At, b, c, K) without MATLAB: the loop above on this package's library (resident plan) and its own cone algebra.
     Returns the dictionary of Sedumi.solve (x, y, cx, by, iter, feasratio, rows = the iteration log, ...)."""
-    return Sedumi(At, b, c, K, hot=hot, pars=pars, device_cone=device_cone, device_qr=device_qr, device_rot=device_rot).solve(verbose=verbose)
+    return Sedumi(At, b, c, K, hot=hot, pars=pars, device_cone=device_cone, device_qr=device_qr, device_rot=device_rot,
+                  device_updt=device_updt).solve(verbose=verbose)

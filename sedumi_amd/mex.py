@@ -707,3 +707,43 @@ def sqrtinv(q, vlab, K):
 def set_rot_lds_budget(nbytes):
     """LDS bytes urotorder's working copy / givensrot's column strip may take (sdm_set_rot_lds_budget), 0 = default."""
     check(capi.lib().sdm_set_rot_lds_budget(C.c_int64(int(nbytes))))
+
+
+# ------------------------------------------------------------- next row (SURVEY 8f N8)
+def triumtriu(x, y, K):
+    """z = triumtriu(x, y, K): Z = triu(X) triu(Y) per PSD block, then the strict lower triangle = the conjugate of the strict upper one
+    (triumtriu.m:40-71; include/sedumi_hip.h at sdm_triumtriu).  x, y: lenud values each or any longer vectors of one length (a whole cone vector),
+    of which the last lenud are taken; only their upper triangles are read.  Returns lenud x 1; the diagonal of a Hermitian block as computed."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    x, y = f64(x), f64(y)
+    if x.size != y.size or x.size < lenud:
+        raise SdmError("triumtriu: size mismatch")
+    z = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_triumtriu(C.byref(Kc), pf(x), pf(y), C.c_int64(x.size), pf(z)))
+    del keep
+    return z.reshape(-1, 1)
+
+
+def updtransfo_psd(ux, u, perm, q, vlab, K, maxu=1.1, frame_kind=FRAME_HOUSEHOLDER):
+    """(u, perm, frame) = the PSD part of updtransfo.m:99-108 as ONE call of the library (include/sedumi_hip.h at sdm_updtransfo_psd):
+        du = triumtriu(ux, u, K); [du, perm, gjc, g] = urotorder(du, K, maxu, perm); q = givensrot(gjc, g, q, K); vinv = sqrtinv(q, vlab, K);
+        [frame, r] = qrK(vinv, K); u = triumtriu(r, du, K)
+    bit-equal to those six calls.  ux, u: lenud values or longer vectors (the last lenud are taken, as triumtriu does); perm: sum(K.s) 1-based values,
+    empty / None = none; q: lenud; vlab as sqrtinv's; frame: qrK's Householder frames (frame_kind 0, lenud + hLen) or the explicit Qb (1, lenud)."""
+    Kc, keep, lenud, slen, lenfr, _, _, _ = _frame_sizes(K, frame_kind)
+    ux, u, q, vlab = f64(ux), f64(u), f64(q), f64(vlab)
+    if ux.size < lenud or u.size < lenud:
+        raise SdmError("triumtriu: size mismatch")
+    ux, u = np.ascontiguousarray(ux[ux.size - lenud:]), np.ascontiguousarray(u[u.size - lenud:])
+    if q.size != lenud:
+        raise SdmError("q size mismatch")
+    pin = None
+    if perm is not None and np.size(perm) > 0:
+        pin = f64(perm)
+        if pin.size != slen:
+            raise SdmError("perm size mismatch")
+    uo, po, fr = np.zeros(lenud), np.zeros(slen), np.zeros(lenfr)
+    check(capi.lib().sdm_updtransfo_psd(C.byref(Kc), pf(ux), pf(u), pf(pin) if pin is not None else None, pf(q), pf(vlab) if vlab.size else None,
+                                        C.c_int64(vlab.size), C.c_double(float(np.asarray(maxu).ravel()[0])), C.c_int(frame_kind), pf(uo), pf(po), pf(fr)))
+    del keep
+    return uo.reshape(-1, 1), po.reshape(-1, 1), fr.reshape(-1, 1)
