@@ -335,6 +335,34 @@ int sdm_updtransfo_psd(const sdm_cone *K, const double *ux, const double *u_in, 
                        const double *q, const double *vlab, sdm_int vlab_len, double maxu, int frame_kind,
                        double *u_out, double *perm_out, double *frame);
 
+/* --- next row: the Cholesky factor of the PSD blocks and the two-sided solve with it (csrc/sdm_psdfact.hip) -- */
+
+/* [ux, ispos] = psdfactor(x, K)   psdfactor.m:44-80.  Per PSD block X = L L^H, computed lower; ux holds L + tril(L,-1)^H (the mirrored copy
+ * sdm_triumtriu speaks of), Im diag = 0.0 on Hermitian blocks.  x: len doubles of which the LAST lenud are taken (:55; len < lenud: "size
+ * mismatch"); ux: lenud doubles.  ONLY THE LOWER TRIANGLE of x and the real part of its diagonal are read, as chol(XX,'lower') does.
+ * A pivot that is not > 0 (<= 0 or NaN) fails the block: *ispos = 0, and when block i is the first that fails ux holds the factors of blocks
+ * 0 .. i-1 and exactly 0.0 from block i's offset to the end (:54, :68-71); otherwise *ispos = 1.
+ * Left-looking by 64-column tile columns over all blocks at once, two launches per tile column (the update merged into both); the tile sums on the
+ * FP64 matrix cores, every entry by substitution against the diagonal tile; a block's bits depend on nothing but the block.
+ * No PSD blocks: returns 0, *ispos = 1, launches nothing. */
+int sdm_psdfactor(const sdm_cone *K, const double *x, sdm_int len, double *ux, int *ispos);
+
+/* y = psdinvscale(ud, x, K)       psdinvscale.m:40-83.  Per PSD block Y = T^{-1} X T^{-H} with T = triu(ud): ONLY THE UPPER TRIANGLE of ud is
+ * read, its diagonal on both planes as stored.  No symmetry of X is assumed.  x: len doubles, the last lenud taken; ud, y: lenud doubles.
+ * Im diag(Y) = 0.0 on Hermitian blocks (:79).  A zero on diag(T) gives what the division gives (Inf / NaN); nothing is checked.
+ * Two passes of nt launches each (W T^H = X by tile columns, T Y = W by tile rows). */
+int sdm_psdinvscale(const sdm_cone *K, const double *ud, const double *x, sdm_int len, double *y);
+
+/* y = psdscale(ud, x, K, transp)  psdscale.m:76-119 for a bare factor ud (no pivot order): Y = T^H X T, T = tril(ud) (transp = 0) or triu(ud);
+ * Im diag(Y) = 0.0.  The kernels of the plan's psdscale (sdm_plan_psdscale) on the block list of K.  Lengths as sdm_psdinvscale. */
+int sdm_psdscale(const sdm_cone *K, const double *ud, const double *x, sdm_int len, int transp, double *y);
+
+/* trydif.m:62-63 / widelen.m:101-103 as one call:  ux = psdfactor(x, K); s = psdscale(ux, z, K).  x, z: len doubles each, uploaded once, the
+ * last lenud taken; ux, s: lenud doubles; ispos as sdm_psdfactor.  The only transfer in the middle is the blocks' flags: with a failed block the
+ * tail of ux is zeroed on the device before it scales z (the .m files ignore ispos there).  Bit-equal to sdm_psdfactor followed by
+ * sdm_psdscale(K, ux, z, len, 0, s). */
+int sdm_trydif_psd(const sdm_cone *K, const double *x, const double *z, sdm_int len, double *ux, double *s, int *ispos);
+
 /* ================================================================ tier (2) */
 typedef struct sdm_plan sdm_plan;
 

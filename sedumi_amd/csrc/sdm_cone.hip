@@ -23,12 +23,11 @@
 // k_triumtriu (row N8): Z = triu(X) triu(Y) + the conjugate mirror of its strict upper triangle (triumtriu.m:63-64), the two ends of the
 // re-pivoting chain of updtransfo.m:99-108; the same blocking on the tiles I <= J, k-tiles I .. J only (see at the kernel).
 #include "sdm_plan.h"
+#include "sdm_cone_dev.h"
 #include <algorithm>
 #include <cstring>
 
 namespace sdm {
-
-struct ConeBlk { const int *n; const int64_t *off, *foff; const int *herm, *loff; };   // per block: order, offset in x / Qb, in frms, Hermitian?, offset in lab
 
 // ---------------------------------------------------------------- frame expansion
 constexpr int FX_T = 256, FX_CW = 8;                   // work-items of a strip's workgroup; columns per wavefront at most
@@ -168,22 +167,6 @@ k_frame_expand(double *qb, const double *frms, ConeBlk B, const int *strips) {
 //   MODE 2  T  = (T1 Qb^H) o jdiv           tiles I >= J, mirrored; diagjdiv folded into the write
 //   MODE 3  Z1 = Qb^H T
 //   MODE 4  Z  = Z1 Qb                      tiles I >= J, mirrored
-constexpr int CN_T = 256, CN_P = 65;
-struct ConeAcc { sdm_double4 t[2][2]; };
-
-__device__ __forceinline__ void cone_mma(ConeAcc &acc, const double *As, const double *Bs, int wave, int lane) {
-  const int rb = 32 * (wave & 1) + (lane & 15), cb = 32 * (wave >> 1) + (lane & 15), kq = lane >> 4;
-#pragma unroll 4
-  for (int kk = 0; kk < 64; kk += 4) {
-    const double a0 = As[(kk + kq) * CN_P + rb], a1 = As[(kk + kq) * CN_P + rb + 16];
-    const double b0 = Bs[(kk + kq) * CN_P + cb], b1 = Bs[(kk + kq) * CN_P + cb + 16];
-    acc.t[0][0] = SDM_MFMA_F64_16x16x4(a0, b0, acc.t[0][0]);
-    acc.t[0][1] = SDM_MFMA_F64_16x16x4(a0, b1, acc.t[0][1]);
-    acc.t[1][0] = SDM_MFMA_F64_16x16x4(a1, b0, acc.t[1][0]);
-    acc.t[1][1] = SDM_MFMA_F64_16x16x4(a1, b1, acc.t[1][1]);
-  }
-}
-
 template <int MODE>
 __global__ void __launch_bounds__(CN_T)
 k_cone_gemm(double *out, const double *in, const double *qb, const double *lab, ConeBlk B, const int *items) {
@@ -383,8 +366,6 @@ void cone_tables(ConeTabs &T, const std::vector<int> &ns, int rsdpN, int n_ud, i
   T.data = (double *)(T.arena.p + w_dat);
   T.lenud = o; T.lenfr = fo; T.lenlab = lo;
 }
-
-static ConeBlk cone_blk(const ConeTabs &T) { ConeBlk B; B.n = T.n; B.off = T.off; B.foff = T.foff; B.herm = T.herm; B.loff = T.loff; return B; }
 
 // qb (lenud doubles, device) = the explicit Qb of the Householder frames frms (lenud + hLen doubles, device)
 void cone_expand(sdm_plan *P, const ConeTabs &T, const double *frms, double *qb) {

@@ -532,4 +532,91 @@ int sdm_updtransfo_psd(const sdm_cone *K, const double *ux, const double *u_in, 
   d2h(frame, ex ? db : dfr, ex ? T.lenud : T.lenfr);
   SDM_CATCH
 }
+// ---- psdfactor, psdinvscale (sdm_psdfact.hip), psdscale for a bare factor, and trydif.m:62-63 as one call; the call shape of N5 - N8
+// the checks the four share, before anything touches a device: K, len >= lenud ("size mismatch"); false: no PSD block has an entry
+static bool fact_checks(const char *who, const sdm_cone *K, sdm_int len, std::vector<int> &ns, sdm_int &lenud) {
+  const bool work = frame_checks(K, SDM_FRAME_HOUSEHOLDER, ns);
+  sdm_int plen;
+  cone_blocks(K, ns, lenud, plen);
+  if (len < lenud) throw std::runtime_error(std::string(who) + ": size mismatch");
+  return work;
+}
+// where block `bad` begins in a lenud vector
+static sdm_int fact_offset(const sdm_cone *K, const std::vector<int> &ns, int bad) {
+  sdm_int o = 0;
+  for (int b = 0; b < bad; b++) o += ((sdm_int)b < K->rsdpN ? 1 : 2) * (sdm_int)ns[b] * ns[b];
+  return o;
+}
+int sdm_psdfactor(const sdm_cone *K, const double *x, sdm_int len, double *ux, int *ispos) {
+  SDM_TRY
+  std::vector<int> ns; sdm_int lenud;
+  const bool work = fact_checks("psdfactor", K, len, ns, lenud);
+  if (ispos) *ispos = 1;
+  if (!work) return 0;
+  FrameCall C("psdfactor", K, SDM_FRAME_HOUSEHOLDER, x && ux && ispos);
+  PsdFactPlan S; psdfact_plan(S, C.ns, (int)K->rsdpN);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 1, 0, 0, S.words());
+  double *da = T.data, *area = da + T.lenud;
+  h2d(da, x + (len - lenud), T.lenud);                                  // psdfactor.m:55: the last lenud entries
+  psdfactor_run(C.p, T, S, area, da);
+  const int bad = psdfactor_first_bad(C.p, S, area);
+  d2h(ux, da, T.lenud);
+  if (bad >= 0) {                                                        // :68-71: `return` with ux zero from the failed block on
+    const sdm_int o = fact_offset(K, ns, bad);
+    std::fill(ux + o, ux + lenud, 0.0);
+    *ispos = 0;
+  }
+  SDM_CATCH
+}
+int sdm_psdinvscale(const sdm_cone *K, const double *ud, const double *x, sdm_int len, double *y) {
+  SDM_TRY
+  std::vector<int> ns; sdm_int lenud;
+  if (!fact_checks("psdinvscale", K, len, ns, lenud)) return 0;
+  FrameCall C("psdinvscale", K, SDM_FRAME_HOUSEHOLDER, ud && x && y);
+  PsdFactPlan S; psdfact_plan(S, C.ns, (int)K->rsdpN);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 2, 0, 0, S.words());
+  double *du = T.data, *dy = du + T.lenud, *area = dy + T.lenud;
+  h2d(du, ud, T.lenud); h2d(dy, x + (len - lenud), T.lenud);
+  psdinvscale_run(C.p, T, S, area, du, dy);
+  C.read_back(y, dy, T.lenud);
+  SDM_CATCH
+}
+int sdm_psdscale(const sdm_cone *K, const double *ud, const double *x, sdm_int len, int transp, double *y) {
+  SDM_TRY
+  std::vector<int> ns; sdm_int lenud;
+  if (!fact_checks("psdscale", K, len, ns, lenud)) return 0;
+  FrameCall C("psdscale", K, SDM_FRAME_HOUSEHOLDER, ud && x && y);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 4, 0, 0);
+  double *du = T.data, *dx = du + T.lenud, *dt = dx + T.lenud, *dy = dt + T.lenud;
+  h2d(du, ud, T.lenud); h2d(dx, x + (len - lenud), T.lenud);
+  pcg_psdscale_tabs(C.p, T.n, T.off, T.herm, T.items_full, T.nfull, transp ? 1 : 0, du, dx, dt, dy);
+  SDM_HIP_CHECK(hipGetLastError());
+  C.read_back(y, dy, T.lenud);
+  SDM_CATCH
+}
+int sdm_trydif_psd(const sdm_cone *K, const double *x, const double *z, sdm_int len, double *ux, double *s, int *ispos) {
+  SDM_TRY
+  std::vector<int> ns; sdm_int lenud;
+  const bool work = fact_checks("trydif_psd", K, len, ns, lenud);
+  if (ispos) *ispos = 1;
+  if (!work) return 0;
+  FrameCall C("trydif_psd", K, SDM_FRAME_HOUSEHOLDER, x && z && ux && s && ispos);
+  PsdFactPlan S; psdfact_plan(S, C.ns, (int)K->rsdpN);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 4, 0, 0, S.words());
+  double *da = T.data, *dz = da + T.lenud, *dt = dz + T.lenud, *ds = dt + T.lenud, *area = ds + T.lenud;
+  h2d(da, x + (len - lenud), T.lenud); h2d(dz, z + (len - lenud), T.lenud);
+  psdfactor_run(C.p, T, S, area, da);                                                                    // trydif.m:62
+  // the one transfer in the middle: the blocks' flags.  With a failed block ux is zero from it on before it scales z, as the two single calls have it
+  const int bad = psdfactor_first_bad(C.p, S, area);
+  if (bad >= 0) {
+    const sdm_int o = fact_offset(K, ns, bad);
+    SDM_HIP_CHECK(hipMemsetAsync(da + o, 0, (size_t)(lenud - o) * sizeof(double), C.p->stream));
+    *ispos = 0;
+  }
+  pcg_psdscale_tabs(C.p, T.n, T.off, T.herm, T.items_full, T.nfull, 0, da, dz, dt, ds);                  // :63
+  SDM_HIP_CHECK(hipGetLastError());
+  C.read_back(ux, da, T.lenud);
+  d2h(s, ds, T.lenud);
+  SDM_CATCH
+}
 }  // extern "C"

@@ -267,5 +267,13 @@ void pcg_psdscale_on(sdm_plan *P, int transp, bool with_perm, const double *in, 
   SDM_KLAUNCH(P, k_psdscale<2>, dim3(A.pcg_ntiles), dim3(PT), 0, out, A.psdtmp.p, A.ufac.p, B, A.pb_items.p, perm, transp,
               (with_perm && transp) ? 1 : 0);
 }
+// the same two launches on the tables of any list of PSD blocks, without a pivot order (sdm_psdscale, sdm_trydif_psd)
+void pcg_psdscale_tabs(sdm_plan *P, const int *bn, const int64_t *boff, const int *bherm, const int *items, int ntiles, int transp, const double *u,
+                       const double *in, double *tmp, double *out) {
+  if (ntiles == 0) return;
+  PsdBlk B; B.n = bn; B.off = boff; B.herm = bherm; B.poff = nullptr;
+  SDM_KLAUNCH(P, k_psdscale<1>, dim3(ntiles), dim3(PT), 0, tmp, in, u, B, items, (const int *)nullptr, transp, 0);
+  SDM_KLAUNCH(P, k_psdscale<2>, dim3(ntiles), dim3(PT), 0, out, (const double *)tmp, u, B, items, (const int *)nullptr, transp, 0);
+}
 
 }  // namespace sdm

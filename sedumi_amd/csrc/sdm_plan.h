@@ -505,6 +505,10 @@ void pcg_prepare(sdm_plan *P);
 void pcg_amul_on(sdm_plan *P, int transp, const double *in, double *out);
 void pcg_vecsym_on(sdm_plan *P, double *x);
 void pcg_psdscale_on(sdm_plan *P, int transp, bool with_perm, const double *in, double *out);
+// the two passes of psdscale.m:76-119 without a pivot order, on the tables of any list of PSD blocks (cone_tables: n, off, herm, every tile):
+// out = T^H in T per block, T = tril(u) (transp = 0) or triu(u); tmp: lenud doubles of scratch; all four distinct, on the device
+void pcg_psdscale_tabs(sdm_plan *P, const int *bn, const int64_t *boff, const int *bherm, const int *items, int ntiles, int transp, const double *u,
+                       const double *in, double *tmp, double *out);
 // sdm_wrappcg.hip: wrapPcg.m / loopPcg.m as one call (sdm_plan_wrappcg)
 void pcg_wrap(sdm_plan *P, const sdm_cgpars *cg, double y0, bool use_rb, bool use_perm, sdm_int *k, sdm_int *info);
 // sdm_dpr1.hip: resident dense-column unit (deninfac.m:58-94)
@@ -608,4 +612,20 @@ void urot_run(sdm_plan *P, const ConeTabs &T, const RotPlan &S, double *area, co
 void givens_plan(RotPlan &S, const std::vector<int> &ns, int rsdpN, const std::vector<int64_t> &goff_compact);
 void givens_run(sdm_plan *P, const ConeTabs &T, const RotPlan &S, double *area, double *y, const int *gjc, const double *g);
 void sqrtinv_run(sdm_plan *P, const ConeTabs &T, const double *q, const double *v, double *y);
+// sdm_psdfact.hip: psdfactor and psdinvscale as tile algorithms over all blocks, one launch per step
+struct PsdFactPlan {                    // host side of one call: the launches of every step of both functions and the image of their item lists
+  struct Step { int first0, nfirst, second0, nsecond; };   // *0 = first item, n* = items (grid size)
+  std::vector<Step> chol;               // tile column J = 0 .. : the diagonal tiles (first), the tiles below them (second)
+  std::vector<Step> pass1, pass2;       // psdinvscale: tile columns nt-1 .. 0 of W T^H = X, tile rows nt-1 .. 0 of T Y = W (first only)
+  std::vector<int64_t> img;             // int32 items, 4 per item
+  int nb = 0;                           // blocks
+  int64_t ws = 0;                       // doubles in front of the items: the blocks' flags (int32)
+  int64_t words() const { return ws + (int64_t)img.size(); }   // doubles the runs need in `area`
+};
+void psdfact_plan(PsdFactPlan &S, const std::vector<int> &ns, int rsdpN);
+// a (lenud doubles, device): x on entry, L + tril(L,-1)^H of every block behind it; a block that met a pivot that is not > 0 has its flag set
+void psdfactor_run(sdm_plan *P, const ConeTabs &T, const PsdFactPlan &S, double *area, double *a);
+int psdfactor_first_bad(sdm_plan *P, const PsdFactPlan &S, const double *area);   // drains the stream; the first flagged block or -1
+// y (lenud doubles, device): x on entry, triu(ud)^{-1} X triu(ud)^{-H} behind it
+void psdinvscale_run(sdm_plan *P, const ConeTabs &T, const PsdFactPlan &S, double *area, const double *ud, double *y);
 }  // namespace sdm

@@ -409,6 +409,8 @@ class Cone:
         return self._pack(out, zero_imag_diag=True)
 
     def psdinvscale(self, ud, x):
+        if self.s.size and getattr(self.ref, "device_fact", False):    # through the library (N9)
+            return vec(self.ref.call("psdinvscale", 1, col(ud[ud.size - self.lenud:]), col(x), self.K))
         import scipy.linalg as sl
         out = []
         for (TT, n), (XX, _) in zip(self._blocks(ud), self._blocks(x)):
@@ -418,6 +420,9 @@ class Cone:
         return self._pack(out, zero_imag_diag=True)
 
     def psdfactor(self, x):
+        if self.s.size and getattr(self.ref, "device_fact", False):    # through the library (N9)
+            ux, ispos = self.ref.call("psdfactor", 2, col(x), self.K)
+            return vec(ux), bool(ispos)
         out = []
         for XX, n in self._blocks(x):
             try:
@@ -490,15 +495,17 @@ class Cone:
 
 # ----------------------------------------------------------------------------------------------- the solver
 class Sedumi:
-    def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False):
+    def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False,
+                 device_fact=False):
         """(At, b, c, K) as the user passes them to sedumi.m, or -- internal=True -- already through pretransfo.m
         (the golden fixtures store the problems that way).  device_cone: the default MEX host answers psdframeit / psdinvjmul
         through the library (NativeMex(device_cone=True)), device_qr: qrK as well (NativeMex(device_qr=True)), device_rot: urotorder, givensrot and
-        sqrtinv (NativeMex(device_rot=True)), device_updt: the PSD part of updtransfo.m:99-108 as one call (NativeMex(device_updt=True));
-        a host given with G keeps its own."""
-        if G is None and (device_cone or device_qr or device_rot or device_updt):
+        sqrtinv (NativeMex(device_rot=True)), device_updt: the PSD part of updtransfo.m:99-108 as one call (NativeMex(device_updt=True)),
+        device_fact: psdfactor and psdinvscale, and the psdfactor + psdscale of trydif.m:62-63 / widelen.m:101-103 as one call
+        (NativeMex(device_fact=True)); a host given with G keeps its own."""
+        if G is None and (device_cone or device_qr or device_rot or device_updt or device_fact):
             from .conemex import NativeMex
-            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot, device_updt=device_updt))
+            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot, device_updt=device_updt, device_fact=device_fact))
         self.G = G or gl.Glue()                                         # (default: this package's own MEX host, sedumi_amd.driver.conemex)
         self.ref = self.G.ref
         self.pars = pars or default_pars()
@@ -793,8 +800,12 @@ class Sedumi:
             halfxz = (x[cn.i1:cn.i2] * z[cn.i1:cn.i2] + cn.ddot(x[cn.i2:cn.i3], z)) / 2
             tmp = halfxz ** 2 - detxz
             lab2q = halfxz + np.sqrt(tmp) if np.all(tmp > 0) else halfxz
-        w["ux"], _ = cn.psdfactor(x)
-        w["s"] = cn.psdscale(w["ux"], z)
+        if cn.s.size and getattr(self.ref, "device_fact", False):     # the two steps below as one call of the library
+            ux, s, _ = self.ref.call("trydif_psd", 3, col(x), col(z), self.K)
+            w["ux"], w["s"] = vec(ux), vec(s)
+        else:
+            w["ux"], _ = cn.psdfactor(x)
+            w["s"] = cn.psdscale(w["ux"], z)
         w["lab"] = np.concatenate((x[:cn.l] * z[:cn.l], detxz / lab2q if cn.nq else np.zeros(0), lab2q, cn.psdeig(w["s"])))
         return w
 
@@ -1187,8 +1198,9 @@ def load_mat(path):
     return At.astype(np.complex128) if np.iscomplexobj(d["c"]) else At, d["b"], d["c"], K
 
 
-def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False):
+def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False,
+          device_fact=False):
     """sedumi(At, b, c, K) without MATLAB: the loop above on this package's library (resident plan) and its own cone algebra.
     Returns the dictionary of Sedumi.solve (x, y, cx, by, iter, feasratio, rows = the iteration log, ...)."""
     return Sedumi(At, b, c, K, hot=hot, pars=pars, device_cone=device_cone, device_qr=device_qr, device_rot=device_rot,
-                  device_updt=device_updt).solve(verbose=verbose)
+                  device_updt=device_updt, device_fact=device_fact).solve(verbose=verbose)

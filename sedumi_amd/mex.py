@@ -747,3 +747,69 @@ def updtransfo_psd(ux, u, perm, q, vlab, K, maxu=1.1, frame_kind=FRAME_HOUSEHOLD
                                         C.c_int64(vlab.size), C.c_double(float(np.asarray(maxu).ravel()[0])), C.c_int(frame_kind), pf(uo), pf(po), pf(fr)))
     del keep
     return uo.reshape(-1, 1), po.reshape(-1, 1), fr.reshape(-1, 1)
+
+
+# ------------------------------------------------------------- next row (SURVEY 8f N9)
+def _psd_tail(who, v, lenud):
+    v = f64(v)
+    if v.size < lenud:
+        raise SdmError(who + ": size mismatch")
+    return v
+
+
+def psdfactor(x, K, nlhs=1):
+    """[ux, ispos] = psdfactor(x, K): X = L L' per PSD block, ux = L + tril(L,-1)' (psdfactor.m:44-80; include/sedumi_hip.h at sdm_psdfactor).
+    x: lenud values or any longer vector (a whole cone vector), of which the last lenud are taken; only the lower triangles and the real part of
+    the diagonals are read.  ispos False: a block is not positive definite and ux is zero from that block on.  Returns ux (lenud x 1), with
+    nlhs > 1 (ux, ispos)."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    x = _psd_tail("psdfactor", x, lenud)
+    ux = np.zeros(lenud, dtype=np.float64)
+    ispos = C.c_int(1)
+    check(capi.lib().sdm_psdfactor(C.byref(Kc), pf(x), C.c_int64(x.size), pf(ux), C.byref(ispos)))
+    del keep
+    return (ux.reshape(-1, 1), bool(ispos.value)) if nlhs > 1 else ux.reshape(-1, 1)
+
+
+def psdinvscale(ud, x, K):
+    """y = psdinvscale(ud, x, K): Y = T \\ X / T' per PSD block with T = triu(ud) (psdinvscale.m:40-83; include/sedumi_hip.h at sdm_psdinvscale).
+    ud: lenud values, of which only the upper triangles are read; x: lenud values or a longer vector (the last lenud are taken), not assumed
+    symmetric.  Returns lenud x 1, Im diag = 0 on Hermitian blocks."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    ud = f64(ud)
+    if ud.size != lenud:
+        raise SdmError("psdinvscale: ud size mismatch")
+    x = _psd_tail("psdinvscale", x, lenud)
+    y = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_psdinvscale(C.byref(Kc), pf(ud), pf(x), C.c_int64(x.size), pf(y)))
+    del keep
+    return y.reshape(-1, 1)
+
+
+def psdscale_u(ud, x, K, transp=False):
+    """y = psdscale(ud, x, K, transp) for a bare factor ud (no pivot order): Y = T' X T per PSD block, T = tril(ud), with transp triu(ud)
+    (psdscale.m:76-119; include/sedumi_hip.h at sdm_psdscale).  Lengths as psdinvscale.  Returns lenud x 1, Im diag = 0 on Hermitian blocks."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    ud = f64(ud)
+    if ud.size != lenud:
+        raise SdmError("psdscale: ud size mismatch")
+    x = _psd_tail("psdscale", x, lenud)
+    y = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_psdscale(C.byref(Kc), pf(ud), pf(x), C.c_int64(x.size), C.c_int(1 if transp else 0), pf(y)))
+    del keep
+    return y.reshape(-1, 1)
+
+
+def trydif_psd(x, z, K):
+    """(ux, s, ispos) = trydif.m:62-63 / widelen.m:101-103 as ONE call of the library (include/sedumi_hip.h at sdm_trydif_psd):
+        [ux, ispos] = psdfactor(x, K); s = psdscale(ux, z, K)
+    bit-equal to psdfactor followed by psdscale_u.  x, z: vectors of one length, lenud or longer (the last lenud are taken)."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    x, z = _psd_tail("trydif_psd", x, lenud), _psd_tail("trydif_psd", z, lenud)
+    if x.size != z.size:
+        raise SdmError("trydif_psd: size mismatch")
+    ux, s = np.zeros(lenud, dtype=np.float64), np.zeros(lenud, dtype=np.float64)
+    ispos = C.c_int(1)
+    check(capi.lib().sdm_trydif_psd(C.byref(Kc), pf(x), pf(z), C.c_int64(x.size), pf(ux), pf(s), C.byref(ispos)))
+    del keep
+    return ux.reshape(-1, 1), s.reshape(-1, 1), bool(ispos.value)

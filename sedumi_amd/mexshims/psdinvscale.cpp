@@ -1,0 +1,15 @@
+// y = psdinvscale(ud,x,K)  -- replaces psdinvscale.m:40-83 (maxstep.m:63); a MEX file of this name shadows the .m file
+#include "mexcommon.h"
+void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+  if (nrhs < 3) mexErrMsgTxt("psdinvscale requires more input arguments.");
+  if (nlhs > 1) mexErrMsgTxt("psdinvscale generates 1 output argument.");
+  ConeK ck; read_cone(prhs[2], ck);
+  if (ck.K.sdpN == 0) { plhs[0] = mxCreateDoubleMatrix(0, 0, mxREAL); return; }          // psdinvscale.m:42-45: y = []
+  sdm_int lenud = 0;
+  for (sdm_int k = 0; k < ck.K.sdpN; k++) lenud += (k < ck.K.rsdpN ? 1 : 2) * ck.K.sdpNL[k] * ck.K.sdpNL[k];
+  if (mxIsSparse(prhs[0]) || mxIsSparse(prhs[1])) mexErrMsgTxt("Sparse inputs not supported by this version of psdinvscale.");
+  const sdm_int len = (sdm_int)numel(prhs[1]);
+  if ((sdm_int)numel(prhs[0]) != lenud || len < lenud) mexErrMsgTxt("psdinvscale: size mismatch");   // :52: the last lenud entries of x
+  plhs[0] = mxCreateDoubleMatrix(lenud, 1, mxREAL);
+  sdm_check(sdm_psdinvscale(&ck.K, mxGetPr(prhs[0]), mxGetPr(prhs[1]), len, mxGetPr(plhs[0])));
+}
