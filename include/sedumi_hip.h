@@ -363,6 +363,29 @@ int sdm_psdscale(const sdm_cone *K, const double *ud, const double *x, sdm_int l
  * sdm_psdscale(K, ux, z, len, 0, s). */
 int sdm_trydif_psd(const sdm_cone *K, const double *x, const double *z, sdm_int len, double *ux, double *s, int *ispos);
 
+/* --- next row: the eigenvalues and eigenvectors of the PSD blocks (csrc/sdm_psdeig.hip) -------------------------------- */
+
+/* [lab, q] = psdeig(x, K)         psdeig.m:44-93.  Per PSD block the eigenvalues of X + X^H, halved, ascending (lab: sum(K.s) doubles), and -- q
+ * not NULL -- the eigenvectors in that order, each of norm 1, Hermitian blocks as [Re; Im] planes (q: lenud doubles).  x: len doubles of which the
+ * LAST lenud are taken (:51; len < lenud: "size mismatch"); the full block is read, no symmetry is assumed, Im of a Hermitian block's diagonal is
+ * not read.  One-sided block Jacobi on 32-wide column blocks over all blocks at once: X + X^H shifted by sigma = 1.5 min(largest absolute row
+ * sum, Frobenius norm) to a positive definite B, sweeps of round-robin steps with three launches each (the pair's Gram matrix on the FP64 matrix
+ * cores, its eigenvectors by a two-sided Jacobi in LDS, the panel's update on the matrix cores), one synchronise per sweep; lab = (column norm
+ * of the converged B V - sigma) / 2.  With q == NULL the same rotations are made: lab is the same bit for bit.  A block's bits depend on nothing
+ * but the block.
+ * *info = -1, or the first block (0-based) that is not done: one with an entry that is not finite, or not converged after SDM_EIG_MAX_SWEEPS
+ * (30) sweeps.  lab and q of every such block are NaN; the other blocks are not affected.  The call still returns 0.
+ * No PSD blocks: returns 0, *info = -1, launches nothing. */
+int sdm_psdeig(const sdm_cone *K, const double *x, sdm_int len, double *lab, double *q, int *info);
+
+/* mineig = minpsdeig(x, K)        minpsdeig.m:40-75: the smallest entry of sdm_psdeig's lab, by the values-only solve and a minimum on the device;
+ * bit-equal to min(lab) (NaN when a block is not done).  The reference's eigs branch for orders above 500 (:68-72) computes the same quantity and
+ * is not restated.  No PSD blocks: *mineig = +Inf. */
+int sdm_minpsdeig(const sdm_cone *K, const double *x, sdm_int len, double *mineig, int *info);
+
+/* the sweeps the calling thread's last sdm_psdeig / sdm_minpsdeig call made (for the timing tool and the tests' reports) */
+int sdm_psdeig_last_sweeps(void);
+
 /* ================================================================ tier (2) */
 typedef struct sdm_plan sdm_plan;
 

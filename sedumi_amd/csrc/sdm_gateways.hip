@@ -4,6 +4,7 @@
 #include "../../include/sedumi_hip.h"
 #include "sdm_plan.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 using namespace sdm;
@@ -619,4 +620,35 @@ int sdm_trydif_psd(const sdm_cone *K, const double *x, const double *z, sdm_int 
   d2h(s, ds, T.lenud);
   SDM_CATCH
 }
+// ---- psdeig and minpsdeig (sdm_psdeig.hip); the call shape of N9
+static thread_local int g_eig_sweeps = 0;                               // the sweeps of the calling thread's last psdeig / minpsdeig call
+static int eig_call(const char *who, const sdm_cone *K, const double *x, sdm_int len, double *lab, double *q, double *mineig, int *info) {
+  std::vector<int> ns; sdm_int lenud;
+  const bool work = fact_checks(who, K, len, ns, lenud);
+  if (info) *info = -1;
+  if (mineig) *mineig = HUGE_VAL;
+  g_eig_sweeps = 0;
+  if (!work) return 0;
+  FrameCall C(who, K, SDM_FRAME_HOUSEHOLDER, x && info && (lab || mineig));
+  PsdEigPlan S; psdeig_plan(S, C.ns, (int)K->rsdpN);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, q ? 3 : 2, 0, 1, S.words());
+  double *dx = T.data, *db = dx + T.lenud, *dv = q ? db + T.lenud : nullptr, *dl = db + (q ? 2 : 1) * T.lenud, *area = dl + T.lenlab;
+  h2d(dx, x + (len - lenud), T.lenud);                                  // psdeig.m:51: the last lenud entries
+  *info = psdeig_run(C.p, T, S, area, dx, db, dv, dl, dx, mineig != nullptr, &g_eig_sweeps);   // (q over x: x is read by the first launch only)
+  if (lab) d2h(lab, dl, T.lenlab);
+  if (q) d2h(q, dx, T.lenud);
+  if (mineig) d2h(mineig, area + S.o_min, 1);
+  return 0;
+}
+int sdm_psdeig(const sdm_cone *K, const double *x, sdm_int len, double *lab, double *q, int *info) {
+  SDM_TRY
+  if (eig_call("psdeig", K, x, len, lab, q, nullptr, info)) return 1;
+  SDM_CATCH
+}
+int sdm_minpsdeig(const sdm_cone *K, const double *x, sdm_int len, double *mineig, int *info) {
+  SDM_TRY
+  if (eig_call("minpsdeig", K, x, len, nullptr, nullptr, mineig, info)) return 1;
+  SDM_CATCH
+}
+int sdm_psdeig_last_sweeps(void) { return g_eig_sweeps; }
 }  // extern "C"

@@ -628,4 +628,26 @@ void psdfactor_run(sdm_plan *P, const ConeTabs &T, const PsdFactPlan &S, double 
 int psdfactor_first_bad(sdm_plan *P, const PsdFactPlan &S, const double *area);   // drains the stream; the first flagged block or -1
 // y (lenud doubles, device): x on entry, triu(ud)^{-1} X triu(ud)^{-H} behind it
 void psdinvscale_run(sdm_plan *P, const ConeTabs &T, const PsdFactPlan &S, double *area, const double *ud, double *y);
+// sdm_psdeig.hip: psdeig / minpsdeig as a one-sided block Jacobi over all blocks, three launches per step of a sweep
+#ifndef SDM_EIG_MAX_SWEEPS
+#define SDM_EIG_MAX_SWEEPS 30           // outer sweeps before a block counts as not done
+#endif
+struct PsdEigPlan {                     // host side of one call: the blocks' column blocks and where the work arrays lie in `area`
+  struct Step { int first0, n, nchunks; };   // first item, items (pairs) of the step, 64-row chunks of its tallest block
+  std::vector<int> ns, ncb;             // orders; 32-wide column blocks per block
+  int nb = 0;                           // blocks
+  int64_t lenlab = 0, maxitems = 0, maxpairs = 0;   // sum of the orders; pairs of a sweep / of a step with every block iterating
+  // offsets in `area` (doubles): sigma and the sweep's measure per block, the minimum, the blocks' status (int32), lab unsorted, the sorting
+  // permutation (int32), the pairs' measures, the sweep's items and blocks (int32), the pairs' G / W (2 planes of 64 x 64 each), the row sums of |A^2| per tile column
+  int64_t o_sig = 0, o_bmeas = 0, o_min = 0, o_status = 0, o_raw = 0, o_perm = 0, o_meas = 0, o_items = 0, o_gw = 0, o_rsq = 0, ws = 0;
+  int64_t words() const { return ws; }
+};
+void psdeig_plan(PsdEigPlan &S, const std::vector<int> &ns, int rsdpN);
+// the item lists of one sweep over the blocks `active` (ascending): 4 int32 per pair (block, p, q, -), step by step
+void psdeig_sweep(const PsdEigPlan &S, const std::vector<int> &active, std::vector<int> &items, std::vector<PsdEigPlan::Step> &steps);
+// x: the blocks (lenud doubles, device); bw, v: lenud doubles of work each, v null for the values alone; lab: lenlab doubles; q: lenud doubles (may
+// be x) when v is given.  Returns the first block that is not done -- its lab and q are NaN -- or -1; want_min: min(lab) at area[S.o_min].
+// The results are complete on return (one synchronise per sweep).  sweeps_out: the sweeps made
+int psdeig_run(sdm_plan *P, const ConeTabs &T, const PsdEigPlan &S, double *area, const double *x, double *bw, double *v, double *lab, double *q,
+               bool want_min, int *sweeps_out);
 }  // namespace sdm

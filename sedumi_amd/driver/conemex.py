@@ -370,7 +370,7 @@ class NativeMex:
     """`.call(name, nlhs, *args)` like a MEX host: the cone algebra above, the hot path and the symbolic analysis through this package's library."""
     error = RuntimeError
 
-    def __init__(self, device_cone=False, device_qr=False, device_rot=False, device_updt=False, device_fact=False):
+    def __init__(self, device_cone=False, device_qr=False, device_rot=False, device_updt=False, device_fact=False, device_eig=False):
         """device_cone: psdframeit / psdinvjmul through the library (sedumi_amd.mex, SURVEY 8f N5) on the explicit frames this module keeps;
         device_qr: qrK through the library too (N6), handing out the same explicit frames;
         device_rot: urotorder, givensrot and sqrtinv through the library (N7) -- gjc and g are then the reference's compact Givens form and the
@@ -378,7 +378,8 @@ class NativeMex:
         device_updt: the PSD part of updtransfo.m:99-108 (triumtriu, urotorder, givensrot, sqrtinv, qrK, triumtriu) as ONE call of the library (N8),
         "updtransfo_psd", which the driver then makes in place of those six steps -- the pivots follow the reference's rule, as with device_rot;
         device_fact: psdfactor and psdinvscale through the library (N9), and "trydif_psd", the psdfactor + psdscale of trydif.m:62-63 /
-        widelen.m:101-103 as ONE call, which the driver then makes in place of those two steps"""
+        widelen.m:101-103 as ONE call, which the driver then makes in place of those two steps;
+        device_eig: psdeig and minpsdeig through the library (N10), the block Jacobi eigensolver of sdm_psdeig.hip"""
         from sedumi_amd import mex
         self._mex = mex
         self.device_cone = bool(device_cone)
@@ -386,6 +387,7 @@ class NativeMex:
         self.device_rot = bool(device_rot)
         self.device_updt = bool(device_updt)
         self.device_fact = bool(device_fact)
+        self.device_eig = bool(device_eig)
         self._native = {"ddot": ddot, "qblkmul": qblkmul, "vecsym": vecsym, "psdframeit": psdframeit, "psdinvjmul": psdinvjmul, "sqrtinv": sqrtinv,
                         "givensrot": givensrot, "partitA": partitA, "extractA": extractA, "findblks": findblks, "sortnnz": sortnnz}
 
@@ -401,6 +403,8 @@ class NativeMex:
             return self._mex.psdfactor(*args, nlhs=nlhs)
         if self.device_fact and name in ("psdinvscale", "trydif_psd"):
             return getattr(self._mex, name)(*args)
+        if self.device_eig and name in ("psdeig", "minpsdeig"):
+            return getattr(self._mex, name)(*args, nlhs=nlhs)
         if self.device_rot and name == "urotorder":
             return self._mex.urotorder(*args, nlhs=nlhs)
         if self.device_rot and name in ("givensrot", "sqrtinv"):

@@ -436,6 +436,15 @@ class Cone:
         return self._pack(out), True
 
     def psdeig(self, x, want_q=False):
+        if self.s.size and getattr(self.ref, "device_eig", False):     # through the library (N10)
+            if want_q:
+                lab, q, info = self.ref.call("psdeig", 3, col(x), self.K)
+            else:                                                      # (the values alone: a block that is not done comes back as NaN)
+                lab = self.ref.call("psdeig", 1, col(x), self.K)
+                info = 0 if np.isnan(lab).any() else -1
+            if info >= 0:                                              # what numpy.linalg.eigh raises when it does not converge
+                raise np.linalg.LinAlgError("psdeig: a block did not converge or is not finite")
+            return (vec(lab), vec(q)) if want_q else vec(lab)
         labs, qs = [], []
         for XX, n in self._blocks(x):
             XX = XX + XX.conj().T
@@ -463,6 +472,11 @@ class Cone:
         return self._pack(out)
 
     def minpsdeig(self, x):
+        if self.s.size and getattr(self.ref, "device_eig", False):     # through the library (N10)
+            m, info = self.ref.call("minpsdeig", 2, col(x), self.K)
+            if info >= 0:
+                raise np.linalg.LinAlgError("minpsdeig: block %d did not converge or is not finite" % info)
+            return float(np.asarray(m).ravel()[0])
         return min(np.linalg.eigvalsh(XX + XX.conj().T).min() for XX, n in self._blocks(x)) / 2
 
     def psdinvjmul(self, lab, frms, b):
@@ -496,16 +510,17 @@ class Cone:
 # ----------------------------------------------------------------------------------------------- the solver
 class Sedumi:
     def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False,
-                 device_fact=False):
+                 device_fact=False, device_eig=False):
         """(At, b, c, K) as the user passes them to sedumi.m, or -- internal=True -- already through pretransfo.m
         (the golden fixtures store the problems that way).  device_cone: the default MEX host answers psdframeit / psdinvjmul
         through the library (NativeMex(device_cone=True)), device_qr: qrK as well (NativeMex(device_qr=True)), device_rot: urotorder, givensrot and
         sqrtinv (NativeMex(device_rot=True)), device_updt: the PSD part of updtransfo.m:99-108 as one call (NativeMex(device_updt=True)),
         device_fact: psdfactor and psdinvscale, and the psdfactor + psdscale of trydif.m:62-63 / widelen.m:101-103 as one call
-        (NativeMex(device_fact=True)); a host given with G keeps its own."""
-        if G is None and (device_cone or device_qr or device_rot or device_updt or device_fact):
+        (NativeMex(device_fact=True)), device_eig: psdeig and minpsdeig (NativeMex(device_eig=True)); a host given with G keeps its own."""
+        if G is None and (device_cone or device_qr or device_rot or device_updt or device_fact or device_eig):
             from .conemex import NativeMex
-            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot, device_updt=device_updt, device_fact=device_fact))
+            G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot, device_updt=device_updt, device_fact=device_fact,
+                                  device_eig=device_eig))
         self.G = G or gl.Glue()                                         # (default: this package's own MEX host, sedumi_amd.driver.conemex)
         self.ref = self.G.ref
         self.pars = pars or default_pars()
@@ -1199,8 +1214,8 @@ def load_mat(path):
 
 
 def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False,
-          device_fact=False):
+          device_fact=False, device_eig=False):
     """sedumi(At, b, c, K) without MATLAB: the loop above on this package's library (resident plan) and its own cone algebra.
     Returns the dictionary of Sedumi.solve (x, y, cx, by, iter, feasratio, rows = the iteration log, ...)."""
     return Sedumi(At, b, c, K, hot=hot, pars=pars, device_cone=device_cone, device_qr=device_qr, device_rot=device_rot,
-                  device_updt=device_updt, device_fact=device_fact).solve(verbose=verbose)
+                  device_updt=device_updt, device_fact=device_fact, device_eig=device_eig).solve(verbose=verbose)

@@ -813,3 +813,45 @@ def trydif_psd(x, z, K):
     check(capi.lib().sdm_trydif_psd(C.byref(Kc), pf(x), pf(z), C.c_int64(x.size), pf(ux), pf(s), C.byref(ispos)))
     del keep
     return ux.reshape(-1, 1), s.reshape(-1, 1), bool(ispos.value)
+
+
+# ------------------------------------------------------------- next row (SURVEY 8f N10)
+def psdeig(x, K, nlhs=1):
+    """[lab, q] = psdeig(x, K): per PSD block the eigenvalues of X + X', halved, ascending, and -- nlhs > 1 -- the eigenvectors in that order, each of
+    norm 1, Hermitian blocks as [Re; Im] planes (psdeig.m:44-93; include/sedumi_hip.h at sdm_psdeig).  x: lenud values or any longer vector (a whole
+    cone vector), of which the last lenud are taken.  Returns lab (sum(K.s) x 1), with nlhs = 2 (lab, q), with nlhs = 3 (lab, q, info): info is -1,
+    or the first block that is not done (an entry that is not finite, or no convergence at the sweep cap), whose lab and q are NaN.  lab is the
+    same bit for bit whether q is asked for or not.  An empty K.s gives the .m file's []."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    x = _psd_tail("psdeig", x, lenud)
+    if _Kfields(K)[2].size == 0:
+        e = np.zeros((0, 0))
+        return (e, e, -1)[:nlhs] if nlhs > 1 else e
+    lab = np.zeros(slen, dtype=np.float64)
+    q = np.zeros(lenud, dtype=np.float64) if nlhs > 1 else None
+    info = C.c_int(-1)
+    check(capi.lib().sdm_psdeig(C.byref(Kc), pf(x), C.c_int64(x.size), pf(lab), pf(q), C.byref(info)))
+    del keep
+    if nlhs <= 1:
+        return lab.reshape(-1, 1)
+    return (lab.reshape(-1, 1), q.reshape(-1, 1), int(info.value))[:nlhs]
+
+
+def minpsdeig(x, K, nlhs=1):
+    """mineig = minpsdeig(x, K): the smallest entry of psdeig's lab, bit for bit, from the values-only solve and a minimum on the device
+    (minpsdeig.m:40-75; include/sedumi_hip.h at sdm_minpsdeig).  Returns 1 x 1 (NaN when a block is not done), with nlhs = 2 (mineig, info); an
+    empty K.s gives the .m file's []."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    x = _psd_tail("minpsdeig", x, lenud)
+    if _Kfields(K)[2].size == 0:
+        return (np.zeros((0, 0)), -1) if nlhs > 1 else np.zeros((0, 0))
+    m, info = C.c_double(0.0), C.c_int(-1)
+    check(capi.lib().sdm_minpsdeig(C.byref(Kc), pf(x), C.c_int64(x.size), C.byref(m), C.byref(info)))
+    del keep
+    out = np.array([[m.value]], dtype=np.float64)
+    return (out, int(info.value)) if nlhs > 1 else out
+
+
+def psdeig_last_sweeps():
+    """the sweeps the calling thread's last psdeig / minpsdeig call made"""
+    return int(capi.lib().sdm_psdeig_last_sweeps())
