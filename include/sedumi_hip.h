@@ -386,6 +386,25 @@ int sdm_minpsdeig(const sdm_cone *K, const double *x, sdm_int len, double *minei
 /* the sweeps the calling thread's last sdm_psdeig / sdm_minpsdeig call made (for the timing tool and the tests' reports) */
 int sdm_psdeig_last_sweeps(void);
 
+/* --- next row: psdjmul (csrc/sdm_cone.hip), and maxstep's and wstruct's PSD parts as one call each ---------------------- */
+
+/* z = psdjmul(x, y, K)   psdjmul.m:40-73: per PSD block Z = (X Y + (X Y)^H) / 2.  x, y: len doubles each, the LAST lenud taken (:50); len < lenud:
+ * "size mismatch", before anything touches a device.  The full blocks of x and y are read: no symmetry is assumed, and Im of a Hermitian block's
+ * diagonal is read as the .m file reads it.  z: lenud doubles, exactly symmetric / Hermitian, Im diag = 0.0.  64 x 64 tiles I <= J on the FP64
+ * matrix cores, both terms X(I,k) Y(k,J) and Y(k,I)^H X(J,k)^H into one accumulator, written twice (mirrored); a block's bits depend on nothing
+ * but the block.  No PSD blocks: returns 0, writes nothing. */
+int sdm_psdjmul(const sdm_cone *K, const double *x, const double *y, sdm_int len, double *z);
+
+/* maxstep.m:63 as one call:  mineig = minpsdeig(psdinvscale(ud, dx, K), K).  ud: lenud doubles; dx: len doubles, the last lenud taken.
+ * Bit-equal to sdm_psdinvscale followed by sdm_minpsdeig; info as sdm_minpsdeig.  One allocation, ud and dx uploaded once, psdinvscale's result
+ * never leaves the device; sdm_psdeig_last_sweeps() reports its sweeps.  No PSD blocks: *mineig = +Inf, *info = -1. */
+int sdm_maxstep_psd(const sdm_cone *K, const double *ud, const double *dx, sdm_int len, double *mineig, int *info);
+
+/* widelen.m:101-104 / trydif.m:62-64 as one call:  [ux, ispos] = psdfactor(x); s = psdscale(ux, z); lab = psdeig(s) (values only).
+ * Bit-equal to sdm_trydif_psd followed by sdm_psdeig(K, s, lenud, lab, NULL, info), a failed block's zeroed tail of ux included.  x, z: len
+ * doubles each, the last lenud taken; ux, s: lenud doubles; lab: sum(K.s) doubles.  No PSD blocks: returns 0, *ispos = 1, *info = -1. */
+int sdm_wstruct_psd(const sdm_cone *K, const double *x, const double *z, sdm_int len, double *ux, double *s, double *lab, int *ispos, int *info);
+
 /* ================================================================ tier (2) */
 typedef struct sdm_plan sdm_plan;
 

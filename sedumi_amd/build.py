@@ -75,7 +75,7 @@ SHIM_DIR = os.path.join(HERE, "mexshims")
 MEX_OUT = os.path.join(LIBDIR, "mex")
 SHIMS = ["getada", "getada1", "getada2", "getada3", "blkchol", "fwblkslv", "bwblkslv", "ordmmdmex", "symfctmex", "choltmpsiz", "cholsplit",
          "symbfwblk", "finsymbden", "dpr1fact", "fwdpr1", "bwdpr1", "invcholfac", "incorder", "adendotd", "adenscale", "psdframeit", "psdinvjmul",
-         "qrK", "urotorder", "givensrot", "sqrtinv", "triumtriu", "psdfactor", "psdinvscale", "psdeig", "minpsdeig"]
+         "qrK", "urotorder", "givensrot", "sqrtinv", "triumtriu", "psdfactor", "psdinvscale", "psdeig", "minpsdeig", "psdjmul"]
 
 
 def _newer(target, deps):

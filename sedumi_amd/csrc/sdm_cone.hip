@@ -22,6 +22,9 @@
 //
 // k_triumtriu (row N8): Z = triu(X) triu(Y) + the conjugate mirror of its strict upper triangle (triumtriu.m:63-64), the two ends of the
 // re-pivoting chain of updtransfo.m:99-108; the same blocking on the tiles I <= J, k-tiles I .. J only (see at the kernel).
+//
+// k_psdjmul (row N11): Z = (X Y + (X Y)^H) / 2 (psdjmul.m:40-73), wregion.m's corrector; the same blocking on the tiles I <= J over all k-tiles,
+// both terms into one accumulator (see at the kernel).
 #include "sdm_plan.h"
 #include "sdm_cone_dev.h"
 #include <algorithm>
@@ -296,6 +299,89 @@ k_triumtriu(double *out, const double *xin, const double *yin, ConeBlk B, const 
   }
 }
 
+// ---------------------------------------------------------------- psdjmul (wregion.m's corrector)
+//   ZZ = X Y;  Z = (ZZ + ZZ^H) / 2                                              psdjmul.m:40-73
+// The blocking of k_triumtriu on the tiles I <= J, without the triangle structure: the full blocks of x and y are read (no symmetry assumed, Im of
+// a Hermitian block's diagonal included) over all nt k-tiles.  (X Y)^H = Y^H X^H, so tile (I, J) of 2 Z is
+//   sum_k  X(I, k) Y(k, J)  +  Y(k, I)^H X(J, k)^H
+// ONE accumulator per output plane over 2 nt k-tiles and no transposition through LDS: the second term stages As[k][row] = conj Y(k, r0 + row),
+// Bs[k][col] = conj X(c0 + col, k).  On planes (the signs go in with the staging of As)
+//   Re = Xr Yr - Xi Yi + Yr^T Xr^T - Yi^T Xi^T          Im = Xr Yi + Xi Yr - Yr^T Xi^T - Yi^T Xr^T
+// Every operand is fetched along its stored column: row fastest for X(I, k) and X(J, k)^H's columns, k fastest for Y(k, J) and Y(k, I).  Rows and
+// columns beyond n are staged as 0.0 and not fetched.  Entries with row <= col are halved (exact) and written to (row, col) and, conjugated, to
+// (col, row) -- on a diagonal tile (r, c) and (c, r) are summed in different orders, hence the mirror there too; Im of a Hermitian diagonal, which
+// the .m file gets as a + (-a), is written as 0.0.  A tile is formed by one workgroup on its own: no hand-over between workgroups, no counters, no
+// atomics, and a block's bits depend on nothing but the block.  Every tile has the same k loop: the order of T.items_up does not matter here.
+__global__ void __launch_bounds__(CN_T)
+k_psdjmul(double *out, const double *xin, const double *yin, ConeBlk B, const int *items) {
+  __shared__ double As[64 * CN_P], Bs[64 * CN_P];
+  const int b = items[4 * blockIdx.x], I = items[4 * blockIdx.x + 1], J = items[4 * blockIdx.x + 2];
+  const int n = B.n[b], herm = B.herm[b];
+  const int64_t nn = (int64_t)n * n;
+  const double *X = xin + B.off[b], *Y = yin + B.off[b];
+  double *O = out + B.off[b];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r0 = 64 * I, c0 = 64 * J;
+  const int nplanes = herm ? 2 : 1;
+  for (int opl = 0; opl < nplanes; opl++) {
+    ConeAcc acc;
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc.t[i][j][r] = 0.0;
+    for (int term = 0; term < nplanes; term++) {
+      const int apl = term, bpl = opl ^ term;
+      // half 0: X Y on planes, Re = Xr Yr - Xi Yi ; Im = Xr Yi + Xi Yr.  half 1: Y^H X^H with A = conj Y^T (planes Yr^T, -Yi^T) and B = conj X^T
+      // (Xr^T, -Xi^T): Re = Yr^T Xr^T - Yi^T Xi^T ; Im = -Yr^T Xi^T - Yi^T Xr^T
+      for (int half = 0; half < 2; half++) {
+        const bool neg = half ? !(opl == 0 && term == 0) : (opl == 0 && term == 1);
+        const double *Am = (half ? Y : X) + (int64_t)apl * nn, *Bm = (half ? X : Y) + (int64_t)bpl * nn;
+        const int ar = half ? 0 : r0, ac = half ? r0 : 0, br = half ? c0 : 0, bc = half ? 0 : c0;    // where the tile begins; kb goes on the other index
+        const int ap = half ? CN_P : 1, aq = half ? 1 : CN_P, bp = half ? 1 : CN_P, bq = half ? CN_P : 1;
+        for (int kb = 0; kb < n; kb += 64) {
+          // f runs along the stored column of both operands; all 32 fetches of a work-item are issued before the first is stored
+          // half 0: As[k = s][row = f] = X(r0 + f, kb + s), Bs[k = f][col = s] = Y(kb + f, c0 + s)
+          // half 1: As[k = f][row = s] = Y(kb + f, r0 + s), Bs[k = s][col = f] = X(c0 + f, kb + s)
+          const int f = tid & 63;
+          const int arow = ar + (half ? kb : 0) + f, brow = br + (half ? 0 : kb) + f;
+          double va[16], vb[16];
+#pragma unroll
+          for (int t = 0; t < 16; t++) {
+            const int s = (tid >> 6) + 4 * t;
+            const int acol = ac + (half ? 0 : kb) + s, bcol = bc + (half ? kb : 0) + s;
+            va[t] = (arow < n && acol < n) ? Am[(int64_t)acol * n + arow] : 0.0;
+            vb[t] = (brow < n && bcol < n) ? Bm[(int64_t)bcol * n + brow] : 0.0;
+          }
+          __syncthreads();
+#pragma unroll
+          for (int t = 0; t < 16; t++) {
+            const int s = (tid >> 6) + 4 * t;
+            As[f * ap + s * aq] = neg ? -va[t] : va[t];
+            Bs[f * bp + s * bq] = vb[t];
+          }
+          __syncthreads();
+          cone_mma(acc, As, Bs, wave, lane);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int row = r0 + 32 * (wave & 1) + 16 * i + (lane >> 4) + 4 * r, col = c0 + 32 * (wave >> 1) + 16 * j + (lane & 15);
+          if (row <= col && col < n) {
+            const double v = (opl == 1 && row == col) ? 0.0 : 0.5 * acc.t[i][j][r];
+            O[(int64_t)opl * nn + (int64_t)col * n + row] = v;
+            O[(int64_t)opl * nn + (int64_t)row * n + col] = (opl == 1 && row != col) ? -v : v;       // (the diagonal: the same value to the same place again)
+          }
+        }
+  }
+}
+
 // =========================================================================== host
 void cone_set_frame_lds_budget(sdm_int bytes) {
   if (bytes < 0 || bytes > FX_LDS_DEFAULT) throw std::runtime_error("frame LDS budget: 0 (default) .. 65536 bytes");
@@ -393,6 +479,12 @@ void cone_invjmul(sdm_plan *P, const ConeTabs &T, const double *qb, const double
 void cone_triumtriu(sdm_plan *P, const ConeTabs &T, const double *x, const double *y, double *z) {
   if (T.nup == 0) return;
   SDM_KLAUNCH(P, k_triumtriu, dim3(T.nup), dim3(CN_T), 0, z, x, y, cone_blk(T), T.items_up);
+  SDM_HIP_CHECK(hipGetLastError());
+}
+// z = (x y + (x y)^H) / 2 per block; everything on the device, z distinct from x and y
+void cone_psdjmul(sdm_plan *P, const ConeTabs &T, const double *x, const double *y, double *z) {
+  if (T.nup == 0) return;
+  SDM_KLAUNCH(P, k_psdjmul, dim3(T.nup), dim3(CN_T), 0, z, x, y, cone_blk(T), T.items_up);
   SDM_HIP_CHECK(hipGetLastError());
 }
 

@@ -595,6 +595,21 @@ int sdm_psdscale(const sdm_cone *K, const double *ud, const double *x, sdm_int l
   C.read_back(y, dy, T.lenud);
   SDM_CATCH
 }
+// trydif.m:62-63 on the device, shared by sdm_trydif_psd and sdm_wstruct_psd: x, z up; da = psdfactor(x), zero from a failed block on; ds = psdscale(da, z)
+static void trydif_steps(FrameCall &C, const sdm_cone *K, const ConeTabs &T, const PsdFactPlan &S, double *area, const double *x, const double *z,
+                         sdm_int len, sdm_int lenud, double *da, double *dz, double *dt, double *ds, int *ispos) {
+  h2d(da, x + (len - lenud), T.lenud); h2d(dz, z + (len - lenud), T.lenud);
+  psdfactor_run(C.p, T, S, area, da);                                                                    // trydif.m:62
+  // the one transfer in the middle: the blocks' flags.  With a failed block ux is zero from it on before it scales z, as the two single calls have it
+  const int bad = psdfactor_first_bad(C.p, S, area);
+  if (bad >= 0) {
+    const sdm_int o = fact_offset(K, C.ns, bad);
+    SDM_HIP_CHECK(hipMemsetAsync(da + o, 0, (size_t)(lenud - o) * sizeof(double), C.p->stream));
+    *ispos = 0;
+  }
+  pcg_psdscale_tabs(C.p, T.n, T.off, T.herm, T.items_full, T.nfull, 0, da, dz, dt, ds);                  // :63
+  SDM_HIP_CHECK(hipGetLastError());
+}
 int sdm_trydif_psd(const sdm_cone *K, const double *x, const double *z, sdm_int len, double *ux, double *s, int *ispos) {
   SDM_TRY
   std::vector<int> ns; sdm_int lenud;
@@ -605,17 +620,7 @@ int sdm_trydif_psd(const sdm_cone *K, const double *x, const double *z, sdm_int 
   PsdFactPlan S; psdfact_plan(S, C.ns, (int)K->rsdpN);
   ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 4, 0, 0, S.words());
   double *da = T.data, *dz = da + T.lenud, *dt = dz + T.lenud, *ds = dt + T.lenud, *area = ds + T.lenud;
-  h2d(da, x + (len - lenud), T.lenud); h2d(dz, z + (len - lenud), T.lenud);
-  psdfactor_run(C.p, T, S, area, da);                                                                    // trydif.m:62
-  // the one transfer in the middle: the blocks' flags.  With a failed block ux is zero from it on before it scales z, as the two single calls have it
-  const int bad = psdfactor_first_bad(C.p, S, area);
-  if (bad >= 0) {
-    const sdm_int o = fact_offset(K, ns, bad);
-    SDM_HIP_CHECK(hipMemsetAsync(da + o, 0, (size_t)(lenud - o) * sizeof(double), C.p->stream));
-    *ispos = 0;
-  }
-  pcg_psdscale_tabs(C.p, T.n, T.off, T.herm, T.items_full, T.nfull, 0, da, dz, dt, ds);                  // :63
-  SDM_HIP_CHECK(hipGetLastError());
+  trydif_steps(C, K, T, S, area, x, z, len, lenud, da, dz, dt, ds, ispos);
   C.read_back(ux, da, T.lenud);
   d2h(s, ds, T.lenud);
   SDM_CATCH
@@ -651,4 +656,59 @@ int sdm_minpsdeig(const sdm_cone *K, const double *x, sdm_int len, double *minei
   SDM_CATCH
 }
 int sdm_psdeig_last_sweeps(void) { return g_eig_sweeps; }
+// ---- psdjmul (sdm_cone.hip), and the two places of the loop that chained two of the calls above through the host as one call each
+int sdm_psdjmul(const sdm_cone *K, const double *x, const double *y, sdm_int len, double *z) {
+  SDM_TRY
+  std::vector<int> ns; sdm_int lenud;
+  if (!fact_checks("psdjmul", K, len, ns, lenud)) return 0;
+  FrameCall C("psdjmul", K, SDM_FRAME_HOUSEHOLDER, x && y && z);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 3, 0, 0);
+  double *dx = T.data, *dy = dx + T.lenud, *dz = dy + T.lenud;
+  h2d(dx, x + (len - lenud), T.lenud); h2d(dy, y + (len - lenud), T.lenud);    // psdjmul.m:50: the last lenud entries of both
+  cone_psdjmul(C.p, T, dx, dy, dz);
+  C.read_back(z, dz, T.lenud);
+  SDM_CATCH
+}
+// maxstep.m:63: psdinvscale's result stays on the device and is minpsdeig's input there
+int sdm_maxstep_psd(const sdm_cone *K, const double *ud, const double *dx, sdm_int len, double *mineig, int *info) {
+  SDM_TRY
+  std::vector<int> ns; sdm_int lenud;
+  const bool work = fact_checks("maxstep_psd", K, len, ns, lenud);
+  if (info) *info = -1;
+  if (mineig) *mineig = HUGE_VAL;
+  g_eig_sweeps = 0;
+  if (!work) return 0;
+  FrameCall C("maxstep_psd", K, SDM_FRAME_HOUSEHOLDER, ud && dx && mineig && info);
+  PsdFactPlan SF; psdfact_plan(SF, C.ns, (int)K->rsdpN);
+  PsdEigPlan SE; psdeig_plan(SE, C.ns, (int)K->rsdpN);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 3, 0, 1, SF.words() + SE.words());
+  double *du = T.data, *dy = du + T.lenud, *db = dy + T.lenud, *dl = db + T.lenud, *area_f = dl + T.lenlab, *area_e = area_f + SF.words();
+  h2d(du, ud, T.lenud); h2d(dy, dx + (len - lenud), T.lenud);
+  psdinvscale_run(C.p, T, SF, area_f, du, dy);
+  *info = psdeig_run(C.p, T, SE, area_e, dy, db, nullptr, dl, dy, true, &g_eig_sweeps);
+  d2h(mineig, area_e + SE.o_min, 1);
+  SDM_CATCH
+}
+// widelen.m:101-104 / trydif.m:62-64: s stays on the device and is psdeig's input there (the values alone; psdeig_run does not write its x)
+int sdm_wstruct_psd(const sdm_cone *K, const double *x, const double *z, sdm_int len, double *ux, double *s, double *lab, int *ispos, int *info) {
+  SDM_TRY
+  std::vector<int> ns; sdm_int lenud;
+  const bool work = fact_checks("wstruct_psd", K, len, ns, lenud);
+  if (ispos) *ispos = 1;
+  if (info) *info = -1;
+  g_eig_sweeps = 0;
+  if (!work) return 0;
+  FrameCall C("wstruct_psd", K, SDM_FRAME_HOUSEHOLDER, x && z && ux && s && lab && ispos && info);
+  PsdFactPlan SF; psdfact_plan(SF, C.ns, (int)K->rsdpN);
+  PsdEigPlan SE; psdeig_plan(SE, C.ns, (int)K->rsdpN);
+  ConeTabs T; cone_tables(T, C.ns, (int)K->rsdpN, 5, 0, 1, SF.words() + SE.words());
+  double *da = T.data, *dz = da + T.lenud, *dt = dz + T.lenud, *ds = dt + T.lenud, *db = ds + T.lenud, *dl = db + T.lenud, *area_f = dl + T.lenlab,
+         *area_e = area_f + SF.words();
+  trydif_steps(C, K, T, SF, area_f, x, z, len, lenud, da, dz, dt, ds, ispos);
+  *info = psdeig_run(C.p, T, SE, area_e, ds, db, nullptr, dl, ds, false, &g_eig_sweeps);
+  d2h(ux, da, T.lenud);
+  d2h(s, ds, T.lenud);
+  d2h(lab, dl, T.lenlab);
+  SDM_CATCH
+}
 }  // extern "C"

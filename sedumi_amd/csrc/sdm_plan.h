@@ -583,6 +583,8 @@ void cone_frameit(sdm_plan *P, const ConeTabs &T, const double *qb, const double
 void cone_invjmul(sdm_plan *P, const ConeTabs &T, const double *qb, const double *xlab, const double *y, double *t1, double *t2, double *z);
 // z = triu(x) triu(y), mirrored, per block (triumtriu.m:63-64); x, y, z: lenud doubles on the device, z none of x, y
 void cone_triumtriu(sdm_plan *P, const ConeTabs &T, const double *x, const double *y, double *z);
+// z = (x y + (x y)^H) / 2 per block (psdjmul.m:40-73): the full blocks are read; z exactly Hermitian, Im diag = 0.0; z distinct from x, y
+void cone_psdjmul(sdm_plan *P, const ConeTabs &T, const double *x, const double *y, double *z);
 // sdm_qrk.hip: [q, r] = qrK(x, K) as a blocked Householder QR with compact-WY trailing updates
 struct QrkSteps {                       // host side of one call: the launches of every panel step and the image of their item tables
   struct Step { int j0, panel0, npanel, strip0, nstrip, tile0, ntile; size_t lds; };

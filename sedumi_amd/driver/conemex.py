@@ -370,7 +370,8 @@ class NativeMex:
     """`.call(name, nlhs, *args)` like a MEX host: the cone algebra above, the hot path and the symbolic analysis through this package's library."""
     error = RuntimeError
 
-    def __init__(self, device_cone=False, device_qr=False, device_rot=False, device_updt=False, device_fact=False, device_eig=False):
+    def __init__(self, device_cone=False, device_qr=False, device_rot=False, device_updt=False, device_fact=False, device_eig=False,
+                 device_jmul=False, device_step=False):
         """device_cone: psdframeit / psdinvjmul through the library (sedumi_amd.mex, SURVEY 8f N5) on the explicit frames this module keeps;
         device_qr: qrK through the library too (N6), handing out the same explicit frames;
         device_rot: urotorder, givensrot and sqrtinv through the library (N7) -- gjc and g are then the reference's compact Givens form and the
@@ -379,7 +380,11 @@ class NativeMex:
         "updtransfo_psd", which the driver then makes in place of those six steps -- the pivots follow the reference's rule, as with device_rot;
         device_fact: psdfactor and psdinvscale through the library (N9), and "trydif_psd", the psdfactor + psdscale of trydif.m:62-63 /
         widelen.m:101-103 as ONE call, which the driver then makes in place of those two steps;
-        device_eig: psdeig and minpsdeig through the library (N10), the block Jacobi eigensolver of sdm_psdeig.hip"""
+        device_eig: psdeig and minpsdeig through the library (N10), the block Jacobi eigensolver of sdm_psdeig.hip;
+        device_jmul: psdjmul through the library (N11);
+        device_step: "maxstep_psd", the psdinvscale + minpsdeig of maxstep.m:63, and "wstruct_psd", the psdfactor + psdscale + psdeig of
+        widelen.m:101-104 / trydif.m:62-64, as ONE call each (N11), which the driver then makes in place of those steps whatever device_fact and
+        device_eig say"""
         from sedumi_amd import mex
         self._mex = mex
         self.device_cone = bool(device_cone)
@@ -388,6 +393,8 @@ class NativeMex:
         self.device_updt = bool(device_updt)
         self.device_fact = bool(device_fact)
         self.device_eig = bool(device_eig)
+        self.device_jmul = bool(device_jmul)
+        self.device_step = bool(device_step)
         self._native = {"ddot": ddot, "qblkmul": qblkmul, "vecsym": vecsym, "psdframeit": psdframeit, "psdinvjmul": psdinvjmul, "sqrtinv": sqrtinv,
                         "givensrot": givensrot, "partitA": partitA, "extractA": extractA, "findblks": findblks, "sortnnz": sortnnz}
 
@@ -405,6 +412,12 @@ class NativeMex:
             return getattr(self._mex, name)(*args)
         if self.device_eig and name in ("psdeig", "minpsdeig"):
             return getattr(self._mex, name)(*args, nlhs=nlhs)
+        if self.device_jmul and name == "psdjmul":
+            return self._mex.psdjmul(*args)
+        if self.device_step and name == "maxstep_psd":
+            return self._mex.maxstep_psd(*args, nlhs=nlhs)
+        if self.device_step and name == "wstruct_psd":
+            return self._mex.wstruct_psd(*args)
         if self.device_rot and name == "urotorder":
             return self._mex.urotorder(*args, nlhs=nlhs)
         if self.device_rot and name in ("givensrot", "sqrtinv"):

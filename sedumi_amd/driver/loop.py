@@ -458,6 +458,8 @@ class Cone:
         return (lab, self._pack(qs)) if want_q else lab
 
     def psdjmul(self, x, y):
+        if self.s.size and getattr(self.ref, "device_jmul", False):    # through the library (N11)
+            return vec(self.ref.call("psdjmul", 1, col(x), col(y), self.K))
         out = []
         for (XX, n), (YY, _) in zip(self._blocks(x), self._blocks(y)):
             ZZ = XX @ YY
@@ -510,17 +512,19 @@ class Cone:
 # ----------------------------------------------------------------------------------------------- the solver
 class Sedumi:
     def __init__(self, At, b, c, K, hot=None, G=None, pars=None, internal=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False,
-                 device_fact=False, device_eig=False):
+                 device_fact=False, device_eig=False, device_jmul=False, device_step=False):
         """(At, b, c, K) as the user passes them to sedumi.m, or -- internal=True -- already through pretransfo.m
         (the golden fixtures store the problems that way).  device_cone: the default MEX host answers psdframeit / psdinvjmul
         through the library (NativeMex(device_cone=True)), device_qr: qrK as well (NativeMex(device_qr=True)), device_rot: urotorder, givensrot and
         sqrtinv (NativeMex(device_rot=True)), device_updt: the PSD part of updtransfo.m:99-108 as one call (NativeMex(device_updt=True)),
         device_fact: psdfactor and psdinvscale, and the psdfactor + psdscale of trydif.m:62-63 / widelen.m:101-103 as one call
-        (NativeMex(device_fact=True)), device_eig: psdeig and minpsdeig (NativeMex(device_eig=True)); a host given with G keeps its own."""
-        if G is None and (device_cone or device_qr or device_rot or device_updt or device_fact or device_eig):
+        (NativeMex(device_fact=True)), device_eig: psdeig and minpsdeig (NativeMex(device_eig=True)), device_jmul: psdjmul
+        (NativeMex(device_jmul=True)), device_step: the PSD parts of maxstep.m:63 and of widelen.m:101-104 / trydif.m:62-64 as one call each
+        (NativeMex(device_step=True)); a host given with G keeps its own."""
+        if G is None and (device_cone or device_qr or device_rot or device_updt or device_fact or device_eig or device_jmul or device_step):
             from .conemex import NativeMex
             G = gl.Glue(NativeMex(device_cone=device_cone, device_qr=device_qr, device_rot=device_rot, device_updt=device_updt, device_fact=device_fact,
-                                  device_eig=device_eig))
+                                  device_eig=device_eig, device_jmul=device_jmul, device_step=device_step))
         self.G = G or gl.Glue()                                         # (default: this package's own MEX host, sedumi_amd.driver.conemex)
         self.ref = self.G.ref
         self.pars = pars or default_pars()
@@ -800,7 +804,13 @@ class Sedumi:
             if np.all(norm2 > 0):
                 norm2 = np.sqrt(norm2)
             mindx = min(mindx, np.min((reltr - norm2) / auxx["tdet"]))
-        if cn.s.size:
+        if cn.s.size and getattr(self.ref, "device_step", False):     # the two steps below as one call of the library (N11)
+            u = auxx["u"]
+            m, info = self.ref.call("maxstep_psd", 2, col(u[u.size - cn.lenud:]), col(dx), self.K)
+            if info >= 0:
+                raise np.linalg.LinAlgError("maxstep_psd: block %d did not converge or is not finite" % info)
+            mindx = min(mindx, float(np.asarray(m).ravel()[0]))
+        elif cn.s.size:
             mindx = min(mindx, cn.minpsdeig(cn.psdinvscale(auxx["u"], dx)))
         return 1.0 / max(-mindx, 1e-16)
 
@@ -815,13 +825,20 @@ class Sedumi:
             halfxz = (x[cn.i1:cn.i2] * z[cn.i1:cn.i2] + cn.ddot(x[cn.i2:cn.i3], z)) / 2
             tmp = halfxz ** 2 - detxz
             lab2q = halfxz + np.sqrt(tmp) if np.all(tmp > 0) else halfxz
-        if cn.s.size and getattr(self.ref, "device_fact", False):     # the two steps below as one call of the library
-            ux, s, _ = self.ref.call("trydif_psd", 3, col(x), col(z), self.K)
-            w["ux"], w["s"] = vec(ux), vec(s)
+        if cn.s.size and getattr(self.ref, "device_step", False):     # the three steps below as one call of the library (N11)
+            ux, s, labs, _, info = self.ref.call("wstruct_psd", 5, col(x), col(z), self.K)
+            if info >= 0:
+                raise np.linalg.LinAlgError("wstruct_psd: block %d did not converge or is not finite" % info)
+            w["ux"], w["s"], labs = vec(ux), vec(s), vec(labs)
         else:
-            w["ux"], _ = cn.psdfactor(x)
-            w["s"] = cn.psdscale(w["ux"], z)
-        w["lab"] = np.concatenate((x[:cn.l] * z[:cn.l], detxz / lab2q if cn.nq else np.zeros(0), lab2q, cn.psdeig(w["s"])))
+            if cn.s.size and getattr(self.ref, "device_fact", False):  # the two steps below as one call of the library
+                ux, s, _ = self.ref.call("trydif_psd", 3, col(x), col(z), self.K)
+                w["ux"], w["s"] = vec(ux), vec(s)
+            else:
+                w["ux"], _ = cn.psdfactor(x)
+                w["s"] = cn.psdscale(w["ux"], z)
+            labs = cn.psdeig(w["s"])
+        w["lab"] = np.concatenate((x[:cn.l] * z[:cn.l], detxz / lab2q if cn.nq else np.zeros(0), lab2q, labs))
         return w
 
     def iswnbr(self, lab, thetaSQR):
@@ -1214,8 +1231,9 @@ def load_mat(path):
 
 
 def solve(At, b, c, K, pars=None, hot=None, verbose=False, device_cone=False, device_qr=False, device_rot=False, device_updt=False,
-          device_fact=False, device_eig=False):
+          device_fact=False, device_eig=False, device_jmul=False, device_step=False):
     """sedumi(At, b, c, K) without MATLAB: the loop above on this package's library (resident plan) and its own cone algebra.
     Returns the dictionary of Sedumi.solve (x, y, cx, by, iter, feasratio, rows = the iteration log, ...)."""
     return Sedumi(At, b, c, K, hot=hot, pars=pars, device_cone=device_cone, device_qr=device_qr, device_rot=device_rot,
-                  device_updt=device_updt, device_fact=device_fact, device_eig=device_eig).solve(verbose=verbose)
+                  device_updt=device_updt, device_fact=device_fact, device_eig=device_eig, device_jmul=device_jmul,
+                  device_step=device_step).solve(verbose=verbose)

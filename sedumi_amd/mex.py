@@ -855,3 +855,50 @@ def minpsdeig(x, K, nlhs=1):
 def psdeig_last_sweeps():
     """the sweeps the calling thread's last psdeig / minpsdeig call made"""
     return int(capi.lib().sdm_psdeig_last_sweeps())
+
+
+# ------------------------------------------------------------- next row (SURVEY 8f N11)
+def psdjmul(x, y, K):
+    """z = psdjmul(x, y, K): Z = (X Y + (X Y)') / 2 per PSD block (psdjmul.m:40-73; include/sedumi_hip.h at sdm_psdjmul).  x, y: lenud values each
+    or any longer vectors of one length (a whole cone vector), of which the last lenud are taken; the full blocks are read, no symmetry assumed.
+    Returns lenud x 1, every block exactly symmetric / Hermitian with Im diag = 0; an empty K.s gives the .m file's []."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    x, y = f64(x), f64(y)
+    if x.size != y.size or x.size < lenud:
+        raise SdmError("psdjmul: size mismatch")
+    z = np.zeros(lenud, dtype=np.float64)
+    check(capi.lib().sdm_psdjmul(C.byref(Kc), pf(x), pf(y), C.c_int64(x.size), pf(z)))
+    del keep
+    return z.reshape(-1, 1)
+
+
+def maxstep_psd(ud, dx, K, nlhs=1):
+    """mineig = maxstep.m:63 as ONE call of the library (include/sedumi_hip.h at sdm_maxstep_psd): minpsdeig(psdinvscale(ud, dx, K), K), bit-equal to
+    those two calls.  ud: lenud values; dx: lenud values or a longer vector (the last lenud are taken).  Returns 1 x 1 (NaN when a block is not done),
+    with nlhs = 2 (mineig, info); without PSD blocks +Inf and -1."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    ud = f64(ud)
+    if ud.size != lenud:
+        raise SdmError("maxstep_psd: ud size mismatch")
+    dx = _psd_tail("maxstep_psd", dx, lenud)
+    m, info = C.c_double(0.0), C.c_int(-1)
+    check(capi.lib().sdm_maxstep_psd(C.byref(Kc), pf(ud), pf(dx), C.c_int64(dx.size), C.byref(m), C.byref(info)))
+    del keep
+    out = np.array([[m.value]], dtype=np.float64)
+    return (out, int(info.value)) if nlhs > 1 else out
+
+
+def wstruct_psd(x, z, K):
+    """(ux, s, lab, ispos, info) = widelen.m:101-104 / trydif.m:62-64 as ONE call of the library (include/sedumi_hip.h at sdm_wstruct_psd):
+        [ux, ispos] = psdfactor(x, K); s = psdscale(ux, z, K); lab = psdeig(s, K)
+    bit-equal to trydif_psd followed by psdeig (the values alone).  x, z: vectors of one length, lenud or longer (the last lenud are taken); info is
+    -1, or the first block of s whose eigenvalues are not done (lab NaN there)."""
+    Kc, keep, lenud, slen, _, _, _, _ = _frame_sizes(K, FRAME_HOUSEHOLDER)
+    x, z = _psd_tail("wstruct_psd", x, lenud), _psd_tail("wstruct_psd", z, lenud)
+    if x.size != z.size:
+        raise SdmError("wstruct_psd: size mismatch")
+    ux, s, lab = np.zeros(lenud, dtype=np.float64), np.zeros(lenud, dtype=np.float64), np.zeros(slen, dtype=np.float64)
+    ispos, info = C.c_int(1), C.c_int(-1)
+    check(capi.lib().sdm_wstruct_psd(C.byref(Kc), pf(x), pf(z), C.c_int64(x.size), pf(ux), pf(s), pf(lab), C.byref(ispos), C.byref(info)))
+    del keep
+    return ux.reshape(-1, 1), s.reshape(-1, 1), lab.reshape(-1, 1), bool(ispos.value), int(info.value)
